@@ -6,9 +6,13 @@
 One "step" = one full `MultirateBetaCondHrrGanRateDistortionTrainer.optimize_parameters` iteration (generator
 forward + no-grad high-rate pass + LPIPS + discriminator passes + backward + clip + Adam for G, aux and D) on a
 device-resident synthetic batch, fp32 end to end (the reference's precision).  Prints ONE JSON line on rank 0.
-`roofline`: the implicit-GEMM conv kernel family (forward + input-gradient launches of igemm_kernel), algorithmic
-FLOPs / HIP-event time per launch, against the dense fp32 MFMA peak.  `cpu_baseline`: the oracle's same step on
-the host cores (bounded sample)."""
+
+A plain run sets up, warms up, times the --steps steps and prints the line.  `--full` adds the measurements that take runs
+of their own: `roofline`, the implicit-GEMM conv kernel family (forward + input-gradient launches of igemm_kernel),
+algorithmic FLOPs / HIP-event time per launch over eager steps after the timed region, against the dense fp32 MFMA peak;
+the fused-op bandwidths, the stage-1 / bf16x3 / bf16x6 / direct-only / no-F(4x4) lines, the data-parallel overlap trace and
+`cpu_baseline`, the oracle's same step on the host cores (bounded sample).  `--dump-outputs DIR` writes what the last timed
+step computed (its logged scalars and a seeded sample of the parameters it left behind) as DIR/<name>.npy."""
 import argparse
 import json
 import os
@@ -165,11 +169,39 @@ def _newest_profile(pattern: str):
     return fs[-1] if fs else None
 
 
-def run_stage(a, stage: int, bs: int, steps: int, warmup: int, profile_steps: int, shape_table=None, precision: str = "fp32") -> dict:
+def step_outputs(tr, log, sample: int = 1 << 20, seed: int = 0) -> dict:
+    """What a caller of the timed step receives, as float arrays: the step's logged scalars (losses, bits per pixel,
+    discriminator outputs) and the parameters it leaves behind -- of each network a fixed, seeded sample of `sample`
+    entries of its parameters flattened in `named_parameters` order (4 MiB each)."""
+    import re
+    import numpy as np
+    import torch
+    out = {}
+    for k, v in (log or {}).items():
+        out["step." + re.sub(r"[^A-Za-z0-9_.-]", "_", k)] = np.asarray(float(v), dtype=np.float64)
+    for name, net in (("generator", tr.comp_model), ("discriminator", getattr(tr, "discriminator", None))):
+        if net is None:
+            continue
+        params = [p.detach().reshape(-1) for _, p in net.named_parameters()]
+        total = sum(p.numel() for p in params)
+        idx = np.sort(np.random.default_rng(seed).choice(total, size=min(sample, total), replace=False))
+        picked, off = [], 0
+        for p in params:
+            lo, hi = np.searchsorted(idx, [off, off + p.numel()])
+            if hi > lo:
+                picked.append(p[torch.from_numpy(idx[lo:hi] - off).to(p.device)])
+            off += p.numel()
+        out[f"{name}_params_sample"] = torch.cat(picked).float().cpu().numpy()
+    return out
+
+
+def run_stage(a, stage: int, bs: int, steps: int, warmup: int, profile_steps: int, shape_table=None, precision: str = "fp32",
+              comm_trace: bool = False, dump: bool = False) -> dict:
     """Build the stage's trainer, warm up (autotune + graph capture per rate index), time `steps` iterations with the rate
     index CYCLED deterministically (q = iteration mod rate levels: the expectation over the uniform draw of the reference,
-    interpca_hyperprior_model.py:28-29, without sampling noise in the step mix), then `profile_steps` eager iterations
-    with HIP events around every conv launch."""
+    interpca_hyperprior_model.py:28-29, without sampling noise in the step mix), then (`dump`) take what the last timed
+    step computed, (`comm_trace`, data parallel) trace the all-reduces over extra steps and run `profile_steps` eager
+    iterations with HIP events around every conv launch."""
     import ctypes as C
     import torch
     import torch.distributed as dist
@@ -178,6 +210,9 @@ def run_stage(a, stage: int, bs: int, steps: int, warmup: int, profile_steps: in
     ws = D.world_size()
     device = f"cuda:{torch.cuda.current_device()}"
     tr = build_trainer(stage, bs, a.size, device, graphs=not a.no_graph, precision=precision)
+    # a single-process trainer draws each step's beta from numpy's global generator (the reference's uniform draw): seeded, so that the
+    # steps of every run see the same inputs
+    __import__("numpy").random.seed(0)
     loader = iter(tr.train_loader)
     lib = __import__("crdr_amd.hip.lib", fromlist=["load"]).load()
     levels = getattr(tr.comp_model, "rate_level", 0)
@@ -195,7 +230,7 @@ def run_stage(a, stage: int, bs: int, steps: int, warmup: int, profile_steps: in
         d = next(loader)
         if levels:
             d = {**d, "rate_ind": (it % levels) if q is None else q}
-        tr.optimize_parameters(it, d)
+        return tr.optimize_parameters(it, d)
     # untimed preparation: autotune every shape eagerly and capture one graph set per rate index (each graph key needs
     # `graph_warmup` eager iterations first)
     for q in (range(levels) if levels else [None]):
@@ -207,17 +242,19 @@ def run_stage(a, stage: int, bs: int, steps: int, warmup: int, profile_steps: in
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]   # per-step device timestamps (no extra syncs): the median
     marks[0].record()
     t0 = time.perf_counter()
+    log = None
     for k in range(steps):
-        step()
+        log = step()
         marks[k + 1].record()   # the step's stream scope has made the current stream wait for the trainer's stream
     barrier()
     dt = time.perf_counter() - t0
     per_step = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(steps))
     median_ms = (per_step[(steps - 1) // 2] + per_step[steps // 2]) / 2 if steps else None
+    outputs = step_outputs(tr, log) if dump else None   # before any further step changes the parameters
     # communication overlap (data parallel): timing events around every gradient all-reduce, over `comm_steps` extra graph-replayed
     # steps (the collectives run between the captured graphs, on the communication stream)
     comm = None
-    if D.is_dist():
+    if comm_trace and D.is_dist():
         D.TRACE = []
         for _ in range(min(10, max(steps, 1))):
             step()
@@ -294,7 +331,7 @@ def run_stage(a, stage: int, bs: int, steps: int, warmup: int, profile_steps: in
                 f.write(f"{ms / max(profile_steps, 1):8.3f} ms/step  {cnt / max(profile_steps, 1):6.1f} calls/step  {fl / (ms * 1e-3) / 1e12:6.1f} TF  "
                         f"[{lo * 1e3:7.1f} .. {hi * 1e3:7.1f} us]  {kind:5s} {label}\n")
     out = {"value": ws * bs * steps / dt, "ms_per_step": dt / steps * 1e3, "median_ms": median_ms, "comm": comm, "igemm": ig, "wgrad": wg,
-           "alg_bytes_per_igemm_launch": alg_bytes, "graphs": bool(graphs_on), "trainer": tr}
+           "alg_bytes_per_igemm_launch": alg_bytes, "graphs": bool(graphs_on), "trainer": tr, "outputs": outputs}
     return out
 
 
@@ -407,8 +444,17 @@ def main():
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "bf16x6"], help="matrix mode of the MAIN line (database builds of the opt-in modes: "
                                                                                             "tools/tune_bf16x6.sh); the default and the headline are exact fp32")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from Python instead of replaying captured HIP graphs")
-    ap.add_argument("--profile-steps", type=int, default=5, help="eager steps after the timed region used for the per-kernel roofline")
+    ap.add_argument("--profile-steps", type=int, default=None, help="eager steps after the timed region used for the per-kernel roofline "
+                                                                    "(default: 5 with --full or --shape-table, else 0 and no roofline)")
+    ap.add_argument("--full", action="store_true", help="also run what takes runs of its own: the per-kernel roofline, the fused-op bandwidths, the "
+                                                        "stage-1 / bf16x3 / bf16x6 / direct-only / no-F(4x4) lines, the data-parallel overlap trace "
+                                                        "and the CPU baseline (--no-secondary / --no-cpu-baseline still drop theirs)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32 / "
+                                                                        "float64): its logged scalars and a seeded sample of the parameters")
     a = ap.parse_args()
+    if a.profile_steps is None:
+        a.profile_steps = 5 if a.full or a.shape_table else 0
+    secondary = a.full and not a.no_secondary
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves.  This parent has not imported torch
@@ -444,8 +490,14 @@ def main():
         ops.load_tune_cache(path, only_kinds=tuple(kinds.split(",")), ignore_signature=True)
     if ops.AUTOTUNE and a.retune_k3:
         ops.load_tune_cache(a.retune_k3, ignore_signature=True, skip=lambda key: (3, 3) in key or (5, 5) in key or (a.retune_k1 and (1, 1) in key))   # (conv launches and weight gradients alike)
-    main_run = run_stage(a, a.stage, a.bs, a.steps, a.warmup, a.profile_steps, a.shape_table, precision=a.precision)
+    main_run = run_stage(a, a.stage, a.bs, a.steps, a.warmup, a.profile_steps, a.shape_table, precision=a.precision, comm_trace=a.full,
+                         dump=bool(a.dump_outputs) and rk == 0)
     tr = main_run.pop("trainer")
+    if main_run["outputs"] is not None:
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in main_run.pop("outputs").items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
     def save_tuning():   # (again at the end: the secondary runs tune their own shapes)
         if rk == 0 and a.save_tune_db:
             ops.save_tune_cache(a.save_tune_db)
@@ -463,7 +515,8 @@ def main():
     # HBM bytes per launch of the dominant kernel come from separate rocprofv3 --pmc passes over one step (counters cannot
     # be read inside this process): tools/pmc_step.py + tools/pmc_families.py, newest result committed under profiles/
     traffic, traffic_src, traffic_nr = None, None, None
-    tp = _newest_profile("r*_hbm_families.json")
+    roofline = a.full or a.profile_steps > 0   # (the roofline reports what the profiled steps measured)
+    tp = _newest_profile("r*_hbm_families.json") if roofline else None
     if a.stage == 3 and a.bs == 16 and a.size == 256 and tp:
         with open(tp) as f:
             doc = json.load(f)
@@ -516,11 +569,12 @@ def main():
             "peak_device_mem_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
             "config": {"workload": f"config/crdr_stage_{a.stage}.yaml -b {a.bs}: full GAN step (G + 5x CLIC21GVAE D + LPIPS-Alex, random-init weights), "
                                    f"rate index cycled 0..4" if a.stage == 3 else f"config/crdr_stage_1.yaml -b {a.bs}: R-D step (+LPIPS-Alex, random-init weights)",
-                       "global_batch": ws * a.bs, "crop": a.size, "parallelism": f"dp{ws}"},
-            "roofline": roof}
+                       "global_batch": ws * a.bs, "crop": a.size, "parallelism": f"dp{ws}"}}
+    if roofline:
+        line["roofline"] = roof
     if main_run.get("comm") is not None:
         line["comm_overlap"] = main_run["comm"]
-    if ws == 1 and not a.no_secondary:
+    if ws == 1 and secondary:
         try:
             roof["fused_ops"] = fused_ops_roofline(tr)
             fp = _newest_profile("r*_hbm_families.json")
@@ -546,7 +600,7 @@ def main():
                                       "whole_step_frac": round(s1["value"] * GFLOP_PER_IMG_STAGE1 / 1e3 / FP32_MFMA_PEAK_TFLOPS, 4)}
             except Exception as e:
                 line["stage1_bs8"] = {"error": repr(e)[:300]}
-    if ws == 1 and a.stage == 3 and (a.bf16x3 or not a.no_secondary):
+    if ws == 1 and a.stage == 3 and (a.bf16x3 or secondary):
         # second line, never the headline: the same step with `precision: bf16x3` (conv / weight-gradient products as split-bf16
         # triples on the bf16 matrix path, <= 3 * 2^-16 relative error per product, fp32 accumulate; everything else as above)
         try:
@@ -567,7 +621,7 @@ def main():
                 "parity": "tests/test_gpu_bf16x3.py: kernels within 3 * 2^-16 * sum|a||b|, step losses <= 1e-3, gradients <= 5e-3 vs the oracle"}
         except Exception as e:
             line["stage3_bf16x3"] = {"error": repr(e)[:300]}
-    if ws == 1 and a.stage == 3 and (a.bf16x6 or not a.no_secondary):
+    if ws == 1 and a.stage == 3 and (a.bf16x6 or secondary):
         # the fp32-EQUIVALENT split: `precision: bf16x6` (three exact bf16 pieces per operand, six products of weight >= 2^-16, fp32 accumulate:
         # per-product error ~2^-23, one fp32 rounding) in the direct kernels -- tiled, streaming 1x1, direct weight gradients; the Winograd
         # kernels stay on the exact fp32 instruction and remain the tuner's choice where they are faster.  Held to the UNCHANGED fp32 parity gates
@@ -594,7 +648,7 @@ def main():
                           "elementwise; the full-size stage-3 / stage-1 steps against the oracle at the fp32 gates of tests/test_gpu_step.py"}
         except Exception as e:
             line["stage3_bf16x6"] = {"error": repr(e)[:300]}
-    if ws == 1 and a.stage == 3 and not a.no_secondary:
+    if ws == 1 and a.stage == 3 and secondary:
         # third line, for the record: the same fp32 step with the Winograd kernels taken out of the tuner's candidates (every conv on
         # the implicit-GEMM / streaming kernels, every weight gradient on the direct slab kernel) -- what the headline would be
         # without minimal filtering.  The 3x3 choices of the last database built before those kernels existed are preloaded.
@@ -621,7 +675,7 @@ def main():
                                           "config": {"workload": f"config/crdr_stage_3.yaml -b {a.bs}, CRDR_WINOGRAD=0 (no minimal-filtering kernels)"}}
         except Exception as e:
             line["stage3_direct_only"] = {"error": repr(e)[:300]}
-    if ws == 1 and a.stage == 3 and not a.no_secondary:
+    if ws == 1 and a.stage == 3 and secondary:
         # fourth line: the same fp32 step with only the F(4x4, 3x3) / F(3x3, 4x4) kernels taken out (F(2x2) + direct kernels: the round-3 plan
         # set) -- what the round-4/5 kernels are worth on their own
         try:
@@ -653,7 +707,7 @@ def main():
             line["stage3_no_f4x4"] = {"error": repr(e)[:300]}
     if ops.TUNE_REJECTED:   # candidates the tuner refused because they disagreed with the built-in plan (a silently de-tuned database is visible)
         line["tune_rejected"] = {"count": len(ops.TUNE_REJECTED), "first": [[repr(k), int(a_), float(f"{d:.3g}")] for k, a_, d in ops.TUNE_REJECTED[:8]]}
-    if ws == 1 and not a.no_cpu_baseline:
+    if ws == 1 and a.full and not a.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(a.stage, a.size)
     save_tuning()
     json_out.write(json.dumps(line) + "\n")
