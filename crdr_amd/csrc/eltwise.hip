@@ -438,7 +438,7 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   return r;
 }
 
-enum { RED_SQDIFF = 0, RED_BCE = 1, RED_SQNORM = 2, RED_DOT = 3 };
+enum { RED_SQDIFF = 0, RED_BCE = 1, RED_SQNORM = 2, RED_DOT = 3, RED_L1 = 4 };
 template <int OP>
 __global__ __launch_bounds__(256) void reduce_kernel(const float* a, const float* b, int64_t n, float target,
                                                      float* partial) {
@@ -446,6 +446,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* a, const float
   float s = 0.f;
   for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < n; e += gridDim.x * 256ll) {
     if (OP == RED_SQDIFF) { const float d = a[e] - b[e]; s += d * d; }
+    if (OP == RED_L1) s += fabsf(a[e] - b[e]);
     if (OP == RED_SQNORM) { const float d = a[e]; s += d * d; }
     if (OP == RED_DOT) s += a[e] * b[e];
     if (OP == RED_BCE) {  // BCEWithLogits(x, t) = max(x,0) - x t + log(1 + exp(-|x|))
@@ -470,6 +471,17 @@ __global__ __launch_bounds__(256) void sqdiff_bwd_kernel(const float* a, const f
   const float k = 2.f * gscale * (g ? g[0] : 1.f);
   for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < n; e += gridDim.x * 256ll) {
     const float d = (a[e] - b[e]) * k;
+    if (da) da[e] = d;
+    if (db) db[e] = -d;
+  }
+}
+// torch.sign: sign(0) = 0
+__global__ __launch_bounds__(256) void l1_bwd_kernel(const float* a, const float* b, int64_t n, const float* g, float gscale,
+                                                     float* da, float* db) {
+  const float k = gscale * (g ? g[0] : 1.f);
+  for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < n; e += gridDim.x * 256ll) {
+    const float x = a[e] - b[e];
+    const float d = x > 0.f ? k : x < 0.f ? -k : 0.f;
     if (da) da[e] = d;
     if (db) db[e] = -d;
   }
@@ -1282,6 +1294,10 @@ extern "C" int crdr_sqdiff_sum(const float* a, const float* b, int64_t n, float*
   CRDR_REQUIRE(b, "sqdiff_sum: null pointer");
   return run_reduce<RED_SQDIFF>(a, b, n, 0.f, out, ws, ws_bytes, s, "sqdiff_sum");
 }
+extern "C" int crdr_l1_sum(const float* a, const float* b, int64_t n, float* out, void* ws, size_t ws_bytes, crdr_stream_t s) {
+  CRDR_REQUIRE(b, "l1_sum: null pointer");
+  return run_reduce<RED_L1>(a, b, n, 0.f, out, ws, ws_bytes, s, "l1_sum");
+}
 extern "C" int crdr_bce_diff_sum(const float* p, const float* q, int64_t n, float target, float* out, void* ws,
                                  size_t ws_bytes, crdr_stream_t s) {
   CRDR_REQUIRE(q, "bce_diff_sum: null pointer");
@@ -1296,6 +1312,14 @@ extern "C" int crdr_sqdiff_bwd(const float* a, const float* b, int64_t n, const 
   if (n == 0) return 0;
   hipLaunchKernelGGL(sqdiff_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(s), a, b, n, g, gscale, da, db);
   CRDR_CHECK_LAUNCH("sqdiff_bwd");
+  return 0;
+}
+extern "C" int crdr_l1_bwd(const float* a, const float* b, int64_t n, const float* g, float gscale, float* da, float* db,
+                           crdr_stream_t s) {
+  CRDR_REQUIRE(a && b, "l1_bwd: null pointer");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(l1_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, as_stream(s), a, b, n, g, gscale, da, db);
+  CRDR_CHECK_LAUNCH("l1_bwd");
   return 0;
 }
 extern "C" int crdr_bce_diff_bwd(const float* p, const float* q, int64_t n, float target, const float* g, float gscale,

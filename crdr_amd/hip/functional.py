@@ -765,20 +765,51 @@ class _SqDiffSum(torch.autograd.Function):
         db = torch.empty_like(fb) if ctx.needs_input_grad[1] else None
         L.check(lib.crdr_sqdiff_bwd(fa.data_ptr(), fb.data_ptr(), fa.numel(), g.contiguous().data_ptr(), 1.0, ops._p(da),
                                     ops._p(db), ops._stream()), "sqdiff_bwd")
+        return _unflat(da, a), _unflat(db, b)
 
-        def back(flat, like):
-            if flat is None:
-                return None
-            like2, ld = ops.nhwc(like) if like.dim() == 4 and not like.is_contiguous() else (like, None)
-            if ld is None:
-                return flat.view(like.shape)
-            n, c, h, w = like2.shape
-            return flat.view(n, h, w, ld).permute(0, 3, 1, 2)[:, :c]
-        return back(da, a), back(db, b)
+
+def _unflat(flat, like):
+    """A gradient computed on `_flat(like)`'s buffer, viewed with `like`'s shape (and NHWC pixel stride)."""
+    if flat is None:
+        return None
+    like2, ld = ops.nhwc(like) if like.dim() == 4 and not like.is_contiguous() else (like, None)
+    if ld is None:
+        return flat.view(like.shape)
+    n, c, h, w = like2.shape
+    return flat.view(n, h, w, ld).permute(0, 3, 1, 2)[:, :c]
 
 
 def sqdiff_sum(a, b):
     return _SqDiffSum.apply(a, b)
+
+
+class _L1Sum(torch.autograd.Function):
+    """sum |a - b| (nn.L1Loss before its mean); gradient sign(a - b), sign(0) = 0"""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        lib = L.load()
+        fa, fb = _same_layout(a, b)
+        out = torch.empty(1, dtype=torch.float32, device=a.device)
+        ws, wsn = ops.workspace(lib.crdr_reduce_workspace(fa.numel()), a.device)
+        L.check(lib.crdr_l1_sum(fa.data_ptr(), fb.data_ptr(), fa.numel(), out.data_ptr(), ws, wsn, ops._stream()), "l1_sum")
+        ctx.save_for_backward(a, b)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        lib = L.load()
+        fa, fb = _same_layout(a, b)
+        da = torch.empty_like(fa) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(fb) if ctx.needs_input_grad[1] else None
+        L.check(lib.crdr_l1_bwd(fa.data_ptr(), fb.data_ptr(), fa.numel(), g.contiguous().data_ptr(), 1.0, ops._p(da), ops._p(db),
+                                ops._stream()), "l1_bwd")
+        return _unflat(da, a), _unflat(db, b)
+
+
+def l1_sum(a, b):
+    return _L1Sum.apply(a, b)
 
 
 class _BceDiffSum(torch.autograd.Function):

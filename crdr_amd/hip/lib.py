@@ -173,6 +173,11 @@ SIGNATURES = {
     "crdr_sqdiff_bwd": (_I, [_P, _P, _I64, _P, _F, _P, _P, _P]),
     "crdr_bce_diff_sum": (_I, [_P, _P, _I64, _F, _P, _P, _SZ, _P]),
     "crdr_bce_diff_bwd": (_I, [_P, _P, _I64, _F, _P, _F, _P, _P, _P]),
+    "crdr_l1_sum": (_I, [_P, _P, _I64, _P, _P, _SZ, _P]),
+    "crdr_l1_bwd": (_I, [_P, _P, _I64, _P, _F, _P, _P, _P]),
+    "crdr_msssim_workspace": (_SZ, [_I, _I, _I, _I]),
+    "crdr_msssim_fwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _SZ, _I, _P, _P]),
+    "crdr_msssim_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _SZ, _P]),
     "crdr_sqnorm": (_I, [_P, _I64, _P, _P, _SZ, _P]),
     "crdr_adam_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _I, _P, _F, _P]),
     "crdr_adam_step_dyn": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _P, _P, _F, _P]),

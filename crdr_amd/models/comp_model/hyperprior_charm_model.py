@@ -293,13 +293,13 @@ class HyperpriorCharmModel(BaseModel):
             while pending:
                 yield pending.popleft().result()
 
-    # ---- validation (bpp / PSNR over a loader)
+    # ---- validation (bpp / PSNR / MS-SSIM over a loader)
     def _validation_conditions(self, **kw) -> List[Tuple[str, Dict]]:
         return [("", {})]
 
     @torch.no_grad()
     def validation(self, dataloader, max_sample_size: int, save_img: bool = False, save_dir: str = "", use_tqdm: bool = False, **kw) -> pd.DataFrame:
-        from crdr_amd.utils.img_utils import calc_psnr, imwrite
+        from crdr_amd.utils.img_utils import calc_ms_ssim, calc_psnr, imwrite
         rows = []
         n = min(len(dataloader), max_sample_size)
         if save_img:
@@ -310,6 +310,7 @@ class HyperpriorCharmModel(BaseModel):
                 out = self.run_model(**data, is_train=False, **cond)
                 row[f"bpp{suffix}"] = out["bpp"].mean().item()
                 row[f"psnr{suffix}"] = calc_psnr(out["real_images"], out["fake_images"], 255)
+                row[f"ms_ssim{suffix}"] = calc_ms_ssim(out["real_images"], out["fake_images"])
                 if save_img:
                     imwrite(os.path.join(save_dir, f"sample_{idx + 1}_fake{suffix}.jpg"), out["fake_images"])
             rows.append(row)

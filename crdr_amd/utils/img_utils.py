@@ -1,5 +1,5 @@
-"""PSNR / image writing with the reference's uint8 TRUNCATION (not rounding) semantics
-(src/utils/img_utils.py:17-42, 79-132): [-1,1] float -> (x+1)/2*255 -> astype(uint8)."""
+"""PSNR / MS-SSIM / image writing with the reference's TRUNCATION (not rounding) semantics
+(src/utils/img_utils.py:17-42, 79-162): [-1,1] float -> (x+1)/2*255 -> astype(uint8) / .int()."""
 from __future__ import annotations
 
 import numpy as np
@@ -28,6 +28,18 @@ def calc_psnr(real: torch.Tensor, fake: torch.Tensor, max_val: float = 255) -> f
     if mse == 0:
         return float("inf")
     return 10.0 * math.log10((255.0 ** 2) / mse)
+
+
+def calc_ms_ssim(real: torch.Tensor, fake: torch.Tensor) -> float:
+    """src/utils/img_utils.py:135-162 on the device: if real.max() <= 1 both images are mapped by (x + 1) / 2 * 255, then
+    both are truncated toward zero (`.int().float()`, fused into the kernel's load) and compared with data range 255.
+    Where the reference's size assertion fires (a side of 160 or less) its bare `except` returns -1; so does this."""
+    from crdr_amd.hip import msssim as MS
+    if min(real.shape[-2:]) <= MS.MIN_SIDE:
+        return -1.0
+    quant = MS.QUANT_255 if bool(real.max() <= 1.0) else MS.QUANT_TRUNC
+    with torch.no_grad():
+        return float(MS._ms_ssim(real, fake, 255.0, quant).item())
 
 
 def imwrite(path: str, t: torch.Tensor) -> None:

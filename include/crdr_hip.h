@@ -550,6 +550,23 @@ int crdr_bce_diff_sum(const float* p, const float* q, int64_t n, float target, f
                       crdr_stream_t s);
 int crdr_bce_diff_bwd(const float* p, const float* q, int64_t n, float target, const float* g, float gscale, float* dp,
                       float* dq, crdr_stream_t s);
+/* out[0] = sum |a-b| ; backward da = sign(a-b) g gscale (sign(0) = 0), db = -da   (distortion_loss.py:49-58, nn.L1Loss) */
+int crdr_l1_sum(const float* a, const float* b, int64_t n, float* out, void* ws, size_t ws_bytes, crdr_stream_t s);
+int crdr_l1_bwd(const float* a, const float* b, int64_t n, const float* g, float gscale, float* da, float* db, crdr_stream_t s);
+
+/* MS-SSIM (pytorch_msssim 1.0.0 ms_ssim with the default 11-tap sigma-1.5 window, weights (0.0448, 0.2856, 0.3001, 0.2363,   */
+/* 0.1333), K = (0.01, 0.03), size_average: distortion_loss.py:61-70 (R = 1 on the raw images), img_utils.py:135-162 (R = 255)). */
+/* x, y: N x H x W NHWC images of C <= 4 channels with pixel stride ldx = ldy = 4, 16-byte aligned; min(H, W) > 160.           */
+/* out[0] = mean over (n, c) of prod_{l<4} relu(CS_l)^w_l relu(S_4)^w_4.  quant: 0 as is, 1 truncate toward zero, 2 map          */
+/* (x + 1) / 2 * 255 then truncate (the metric's cvt_range_to_255 / .int().float(), on the load).  `state` (from                 */
+/* crdr_msssim_workspace(N, H, W, with_maps)) keeps the pyramid, the per-level statistics and, with with_maps = 1 (quant = 0     */
+/* only), the per-pixel maps the backward reads; it must live until crdr_msssim_bwd.  Deterministic (no float atomics).         */
+/* crdr_msssim_bwd: dx / dy (either may be NULL; ld 4) = gout[0] * d out / d x, d y; ws from crdr_msssim_workspace(N, H, W, 2).  */
+size_t crdr_msssim_workspace(int N, int H, int W, int which); /* which: 0 / 1 forward state without / with maps, 2 backward ws */
+int crdr_msssim_fwd(const float* x, int ldx, const float* y, int ldy, int N, int H, int W, int C, float data_range, int quant,
+                    float* state, size_t state_bytes, int with_maps, float* out, crdr_stream_t s);
+int crdr_msssim_bwd(const float* x, int ldx, const float* y, int ldy, int N, int H, int W, int C, const float* state,
+                    const float* gout, float* dx, int lddx, float* dy, int lddy, void* ws, size_t ws_bytes, crdr_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------ */
 /* optimiser (build_optimizer_scheduler.py:11-19; rate_distortion_trainer.py:83-85)                  */
