@@ -6,6 +6,7 @@ to the kernels in place through its pixel stride (`ld`).  All arithmetic happens
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -51,13 +52,13 @@ _algo_cache = {}
 TUNE_LOG = []
 
 
-TUNE_ROUNDS = int(__import__("os").environ.get("CRDR_TUNE_ROUNDS", "1"))  # >1: best of several timings (perf-database builds)
+TUNE_ROUNDS = int(os.environ.get("CRDR_TUNE_ROUNDS", "1"))  # >1: best of several timings (perf-database builds)
 
 
 # CRDR_TUNE_COLD=1: evict L2 / Infinity Cache (a 512 MB read-modify-write) before every timed launch.  Inside a training step
 # a conv finds its weights and activations cold -- the producer ran on other XCDs, 100+ MB of other tensors ago -- while
 # back-to-back timing of one launch measures the cache-warm case, which favours configurations with more, smaller loads.
-TUNE_COLD = __import__("os").environ.get("CRDR_TUNE_COLD", "0") == "1"
+TUNE_COLD = os.environ.get("CRDR_TUNE_COLD", "0") == "1"
 _evict = None
 
 
@@ -97,8 +98,8 @@ def _time_call(fn, reps: int = 2) -> float:
     return best
 
 
-WINOGRAD = __import__("os").environ.get("CRDR_WINOGRAD", "1") != "0"   # 0: the tuner never offers the Winograd kernel
-WINO4 = __import__("os").environ.get("CRDR_WINO4", "1") != "0"         # 0: ... never the F(4x4, 3x3) / F(3x3, 4x4) kernels (F(2x2) stays)
+WINOGRAD = os.environ.get("CRDR_WINOGRAD", "1") != "0"   # 0: the tuner never offers the Winograd kernel
+WINO4 = os.environ.get("CRDR_WINO4", "1") != "0"         # 0: ... never the F(4x4, 3x3) / F(3x3, 4x4) kernels (F(2x2) stays)
 
 
 # Tests: every convolution a Winograd kernel accepts takes it (without the tuner, whose choice is per shape and speed): the
@@ -175,7 +176,7 @@ def on_replay(fn) -> None:
         REPLAY_HOOKS.append(fn)
 
 
-FILTER_CACHE_BUDGET = int(__import__("os").environ.get("CRDR_FILTER_CACHE_GB", "24")) << 30   # bytes of transformed filters kept (least recently used go first)
+FILTER_CACHE_BUDGET = int(os.environ.get("CRDR_FILTER_CACHE_GB", "24")) << 30   # bytes of transformed filters kept (least recently used go first)
 _filter_tick = [0]
 
 
@@ -335,12 +336,12 @@ def _demote_if_misaligned(d, ios, G: int, explicit: bool) -> None:
                 return
 
 
-def _launch_conv(lib, d, ios, G: int, ws, ws_n, wkeys, device):
+def _launch_conv(lib, d, ios, G: int, ws, ws_n, device):
     """crdr_conv2d_grouped, through the persistent filter cache where the launch runs the F(4x4) kernel on registered weight packs."""
-    if (d.reserved & 0xFF) == _wino4_id() and all(_is_persistent_pack(int(p_)) for p_ in wkeys):
+    if (d.reserved & 0xFF) == _wino4_id() and all(_is_persistent_pack(int(ios[g].w)) for g in range(G)):
         # (the key leaves the K-split bits of the algorithm id out on purpose: the block layout of the transformed filters does not depend
         # on the split count -- wino4_filter_bytes / wino4_filter_thread take no nsplit)
-        wk = tuple(int(p_) for p_ in wkeys)
+        wk = tuple(int(ios[g].w) for g in range(G))
         key = (wk, G, d.reserved & 0xFF, d.N, d.H, d.W, d.C, d.OH, d.OW, d.OC, d.kh, d.kw, d.stride, d.pad, d.transposed, d.wrows, d.wcols)
         ent = _filter_cache.get(key)
         if ent is not None and not ent.alive():   # (a pack died and its address was reused: drop, never trust)
@@ -381,20 +382,19 @@ _tune_filters = {}
 _tune_w4_penalty = [0.0]
 
 
-def _tune_conv_launch(lib, d, ios, G: int, w_, wn_, device) -> bool:
-    """ios: one lib.ConvIO (G = 1) or a ctypes array of G of them"""
+def _conv_workspace(lib, d, G: int, device):
+    nb = lib.crdr_conv2d_grouped_workspace(C.byref(d), G)
+    return workspace(nb, device, conv=True) if nb else (None, 0)
+
+
+def _tune_conv_launch(lib, d, ios, G: int, device) -> bool:
     _tune_w4_penalty[0] = 0.0
-    if isinstance(ios, L.ConvIO):
-        ios = (L.ConvIO * 1)(ios)
-    if (d.reserved & 0xFF) != _wino4_id():
-        return lib.crdr_conv2d_grouped(C.byref(d), ios, G, w_, wn_, _stream()) == 0
-    nb = int(lib.crdr_conv2d_filter_cache_bytes(C.byref(d), G))
-    if not nb:
-        return lib.crdr_conv2d_grouped(C.byref(d), ios, G, w_, wn_, _stream()) == 0
+    w_, wn_ = _conv_workspace(lib, d, G, device)
+    nb = int(lib.crdr_conv2d_filter_cache_bytes(C.byref(d), G)) if (d.reserved & 0xFF) == _wino4_id() else 0
     wk = tuple(int(ios[g].w) for g in range(G))
-    if not all(_is_persistent_pack(p_) for p_ in wk) or torch.cuda.is_current_stream_capturing():
-        # the real launch will not find a cache (sub-block / temporary packs, or a launch first seen under capture): it transforms on every call,
-        # and that is what the candidate is timed with
+    if not nb or not all(_is_persistent_pack(p_) for p_ in wk) or torch.cuda.is_current_stream_capturing():
+        # (no transformed filters, or) the real launch will not find a cache (sub-block / temporary packs, or a launch first seen under
+        # capture): it transforms on every call, and that is what the candidate is timed with
         return lib.crdr_conv2d_grouped(C.byref(d), ios, G, w_, wn_, _stream()) == 0
     key = (wk, tuple(pack_version(p_) for p_ in wk), G, d.N, d.H, d.W, d.C, d.OH, d.OW, d.OC, d.kh, d.kw, d.stride, d.pad, d.transposed, d.wrows, d.wcols)
     ent = _tune_filters.get(key)
@@ -493,7 +493,7 @@ def _tune_scratch(nfloats: int, device):
     return scratch, (lambda: scratch.copy_(pattern))
 
 
-DEFAULT_TUNE_DB = __import__("os").path.join(__import__("os").path.dirname(__file__), "tune_gfx950.json")
+DEFAULT_TUNE_DB = os.path.join(os.path.dirname(__file__), "tune_gfx950.json")
 
 
 def _tune_signature() -> str:
@@ -515,7 +515,6 @@ def load_tune_cache(path: str, only_kinds=None, ignore_signature: bool = False, 
     (key[0]: "c" / "g" / "m" conv launches, "w" / "wm" weight gradients)."""
     import ast
     import json
-    import os
     if not os.path.exists(path):
         return 0
     with open(path) as f:
@@ -679,6 +678,137 @@ def pack_weight(w: torch.Tensor, transpose: bool) -> torch.Tensor:
 _SPAN_LIMIT = (1 << 31) - (1 << 20)  # operand byte span the conv kernels address with one buffer descriptor
 
 
+def _colsum_layout(lib, d, G: int):
+    """-> (rows, ld, floats) of every problem's CRDR_EPI_COLSUM partial rows under the plan in d"""
+    rows, ld = C.c_int(), C.c_int()
+    L.check(lib.crdr_conv2d_colsum_layout(C.byref(d), G, C.byref(rows), C.byref(ld)), "conv2d_colsum_layout")
+    return rows.value, ld.value, max(1, rows.value * 2 * ld.value)
+
+
+def _conv(lib, d, ios, G: int, key, device, *, flops: float, label: str, nbytes: float, algo: int = 0, plan_as: int = 0,
+          colsum: bool = False, trial_out: Optional[torch.Tensor] = None):
+    """Plan and launch the G convolutions that d and ios (a ctypes array of G lib.ConvIO) describe, and record their profile entry.
+    The plan: an explicit id (`algo`, else FORCED_CONV_ALGO), else the Winograd kernel PREFER_WINOGRAD asks for, else the tuned plan of
+    `key` (AUTOTUNE; None: this launch is never tuned), else the plan the library would give a launch of `plan_as` problems, else the
+    built-in plan.  colsum: the launch carries CRDR_EPI_COLSUM; -> [(partial-row address, rows, ld)] per problem, in colsum_queue(device)'s
+    arena (None without colsum).  trial_out: conv2d_raw's output, which its tuner trials run in (the launch writes it afterwards) -- the
+    scratch outputs of the other launches draw their pattern from torch's generator."""
+    forced = algo or FORCED_CONV_ALGO
+    wino = 0 if forced else _prefer_wino(d, G)
+    GP = plan_as or G
+    if forced or wino:
+        d.reserved = forced or wino
+    elif AUTOTUNE and key is not None and (GP == G or key in _algo_cache):
+        algo = _algo_cache.get(key)
+        if algo is None:
+            if trial_out is not None:
+                tio, res_t, reset = ios, trial_out, None
+            else:
+                # trials run on scratch outputs with the same strides (timing runs would accumulate into live data; and the tuner
+                # compares every candidate's result with the baseline plan's on a tensor it owns)
+                span = (d.N * d.OH * d.OW - 1) * d.ldy + d.OC
+                res_t, reset = _tune_scratch(G * span + 64, device)
+                tio = (L.ConvIO * G)()
+                C.memmove(tio, ios, C.sizeof(tio))
+                for g in range(G):
+                    tio[g].y = res_t.data_ptr() + 4 * g * span
+                    if ios[g].pre == ios[g].y:
+                        tio[g].pre = tio[g].y
+                    if ios[g].res == ios[g].y:
+                        tio[g].res = tio[g].y
+            keep = []
+
+            def run(a):
+                d.reserved = a
+                if colsum:   # (the layout of the partial rows depends on the plan)
+                    try:
+                        _, _, nf = _colsum_layout(lib, d, G)
+                    except L.CrdrHipError:
+                        return False
+                    keep[:] = [torch.empty(G * nf, dtype=torch.float32, device=device)]
+                    for g in range(G):
+                        tio[g].cs = keep[0].data_ptr() + 4 * g * nf
+                return _tune_conv_launch(lib, d, tio, G, device)
+            algo = _autotune(key, lib.crdr_conv2d_num_configs(), 4, run, extra=_stream_ids(), result=lambda: res_t, reset=reset,
+                             agree=TUNE_AGREE["conv"], penalty=lambda: _tune_w4_penalty[0])
+        d.reserved = algo
+    elif GP != G:
+        d.reserved = lib.crdr_conv2d_choose_algo(C.byref(d), GP)
+    _demote_if_misaligned(d, ios, G, bool(forced))
+    cs = None
+    if colsum:
+        rows, ld, nf = _colsum_layout(lib, d, G)
+        q = colsum_queue(device)
+        cs = [(q.alloc(nf), rows, ld) for _ in range(G)]
+        for g in range(G):
+            ios[g].cs = cs[g][0]
+    ws, ws_n = _conv_workspace(lib, d, G, device)
+    e0 = _prof_begin()
+    L.check(_launch_conv(lib, d, ios, G, ws, ws_n, device), "conv2d_grouped")
+    _prof_end("igemm", flops, e0, label, nbytes)
+    return cs
+
+
+def _wgrad(lib, d, G: int, ps, qs, gs, key, device, *, flops: float, label: str, whole: bool = False, algo: int = 0,
+           defer: bool = True) -> list:
+    """Plan and launch the G weight gradients that d describes (operand / gradient addresses ps, qs, gs), and record their profile entry.
+    The plan: the explicit `algo`, else the tuned plan of `key` (AUTOTUNE), else the built-in plan.  A tuner trial runs the complete weight
+    gradient with accumulate = 0 (`whole`), or the slab launch and the batched reduce that a deferred launch takes.  The slabs' reduction
+    is deferred onto WGRAD_DEFER (defer=False: reduced inside the same call); -> the jobs queued there, for the caller to adjust."""
+    pa, qa, ga = ((C.c_void_p * G)(*v) for v in (ps, qs, gs))
+    if algo:
+        d.algo = _wa(algo)
+    elif AUTOTUNE:
+        algo = _algo_cache.get(key)
+        if algo is None:
+            gsize = d.gI * d.gJ * d.kh * d.kw
+            tmp = torch.zeros(G * gsize + 64, dtype=torch.float32, device=device)
+            ta = (C.c_void_p * G)(*[tmp.data_ptr() + 4 * g * gsize for g in range(G)])
+            jobs_t = (L.WgradJob * G)()
+            slab = [0]
+            accumulate = d.accumulate
+            if whole:
+                d.accumulate = 0
+
+            def run(a):
+                d.algo = _wa(a)
+                nb = lib.crdr_conv2d_wgrad_grouped_workspace(C.byref(d), G)
+                if nb == 0 or nb > (2 << 30):
+                    return False
+                slab[0] = nb
+                w_, wn_ = workspace(nb, device)
+                if whole:
+                    return lib.crdr_conv2d_wgrad(C.byref(d), pa[0], qa[0], ta[0], w_, wn_, _stream()) == 0
+                return lib.crdr_conv2d_wgrad_partial_grouped(C.byref(d), pa, qa, ta, G, w_, wn_, jobs_t, _stream()) == 0
+            if whole:
+                result, reset, penalty = (lambda: tmp), None, None
+            else:
+                def result():   # the trial's slabs reduced into tmp (the jobs accumulate: tmp is zeroed by reset())
+                    reduce_jobs_now(jobs_t, device)
+                    return tmp
+                # + the batched reduce's read of these slabs at its measured 3.8 TB/s (profiles/r2_h_hbm_families.json)
+                reset, penalty = tmp.zero_, (lambda: slab[0] / 3.8e9)
+            algo = _autotune(key, lib.crdr_conv2d_wgrad_num_configs(), 8, run, extra=_wgrad_wino4_ids(), penalty=penalty, result=result,
+                             reset=reset, agree=TUNE_AGREE["wgrad"])
+            d.accumulate = accumulate
+        d.algo = _wa(algo)
+    nbytes = lib.crdr_conv2d_wgrad_grouped_workspace(C.byref(d), G)
+    e0 = _prof_begin()
+    queued = []
+    if defer:
+        assert WGRAD_DEFER is not None, "this launch needs deferred weight-gradient reductions (ops.WGRAD_DEFER)"
+        jobs = (L.WgradJob * G)()
+        L.check(lib.crdr_conv2d_wgrad_partial_grouped(C.byref(d), pa, qa, ga, G, WGRAD_DEFER.alloc(nbytes), nbytes, jobs, _stream()),
+                "conv2d_wgrad_partial_grouped")
+        queued = [L.WgradJob.from_buffer_copy(jb) for jb in jobs]
+        WGRAD_DEFER.jobs += queued
+    else:
+        ws, ws_n = workspace(nbytes, device)
+        L.check(lib.crdr_conv2d_wgrad(C.byref(d), pa[0], qa[0], ga[0], ws, ws_n, _stream()), "conv2d_wgrad")
+    _prof_end("wgrad", flops, e0, label)
+    return queued
+
+
 def conv_out_size(h, k, stride, pad, transposed, out_pad=0):
     if transposed:
         return (h - 1) * stride - 2 * pad + k + out_pad
@@ -717,31 +847,12 @@ def conv2d_raw(x: torch.Tensor, wpack: torch.Tensor, oc: int, k: Tuple[int, int]
             ldg = oc
         d.ldg = ldg
         io.gx, io.gt, io.sig = gate_x.data_ptr(), gate_t.data_ptr(), sig_out.data_ptr()
-    explicit = bool(algo or FORCED_CONV_ALGO)
-    if explicit:
-        d.reserved = algo or FORCED_CONV_ALGO
-    elif _prefer_wino(d):
-        d.reserved = _prefer_wino(d)
-    elif AUTOTUNE and not (flags & L.EPI_ACCUM):
-        key = ("c", n, h, w, d.C, oh, ow, oc, k, stride, pad, int(transposed), ldx, ldy, flags, d.ldres, d.ldg, wlayout)
-        algo = _algo_cache.get(key)
-        if algo is None:
-            def run(a):
-                d.reserved = a
-                nb = lib.crdr_conv2d_workspace(C.byref(d))
-                w_, wn_ = workspace(nb, x.device, conv=True) if nb else (None, 0)
-                return _tune_conv_launch(lib, d, io, 1, w_, wn_, x.device)
-            algo = _autotune(key, lib.crdr_conv2d_num_configs(), 4, run, extra=_stream_ids(), result=lambda: out_t,
-                             agree=TUNE_AGREE["conv"], penalty=lambda: _tune_w4_penalty[0])
-        d.reserved = algo
-    _demote_if_misaligned(d, (io,), 1, explicit)
-    nbytes = lib.crdr_conv2d_workspace(C.byref(d))
-    ws, ws_n = workspace(nbytes, x.device, conv=True) if nbytes else (None, 0)
-    e0 = _prof_begin()
-    L.check(_launch_conv(lib, d, C.byref(io), 1, ws, ws_n, (wpack.data_ptr(),), x.device), "conv2d")
-    _prof_end("igemm", 2.0 * n * (h * w if transposed else oh * ow) * c * oc * k[0] * k[1], e0,
-              f"{'T' if transposed else 'C'} {c}->{oc} k{k[0]}s{stride} in{h}x{w} f{flags}",
-              4.0 * (n * h * w * c + n * oh * ow * oc * (1 + (res is not None) + 3 * (gate_x is not None)) + k[0] * k[1] * c * oc))
+    key = None if flags & L.EPI_ACCUM else ("c", n, h, w, d.C, oh, ow, oc, k, stride, pad, int(transposed), ldx, ldy, flags, d.ldres,
+                                            d.ldg, wlayout)
+    _conv(lib, d, (L.ConvIO * 1)(io), 1, key, x.device, algo=algo, trial_out=out_t,
+          flops=2.0 * n * (h * w if transposed else oh * ow) * c * oc * k[0] * k[1],
+          label=f"{'T' if transposed else 'C'} {c}->{oc} k{k[0]}s{stride} in{h}x{w} f{flags}",
+          nbytes=4.0 * (n * h * w * c + n * oh * ow * oc * (1 + (res is not None) + 3 * (gate_x is not None)) + k[0] * k[1] * c * oc))
     return out
 
 
@@ -768,36 +879,10 @@ def conv2d_wgrad_raw(p: torch.Tensor, q: torch.Tensor, g: torch.Tensor, k, strid
     assert g.is_contiguous() and g.shape[0] <= pc4 and g.shape[1] <= qc4
     d = L.WgradDesc(N=n, PH=ph, PW=pw, PC=pc4, ldp=ldp, QH=qh, QW=qw, QC=qc4, ldq=ldq, kh=k[0], kw=k[1],
                     stride=stride, pad=pad, gI=g.shape[0], gJ=g.shape[1], accumulate=int(accumulate), algo=_wa(0))
-    if algo:
-        d.algo = _wa(algo)
-    elif AUTOTUNE:
-        key = ("w", n, ph, pw, pc4, ldp, qh, qw, qc4, ldq, k, stride, pad, g.shape[0], g.shape[1]) + _mk()
-        algo = _algo_cache.get(key)
-        if algo is None:
-            tmp = torch.zeros_like(g)
-
-            def run(a):
-                d.algo, d.accumulate = _wa(a), 0
-                nb = lib.crdr_conv2d_wgrad_workspace(C.byref(d))
-                if nb > (2 << 30):
-                    return False
-                w_, wn_ = workspace(nb, p.device)
-                return lib.crdr_conv2d_wgrad(C.byref(d), p.data_ptr(), q.data_ptr(), tmp.data_ptr(), w_, wn_, _stream()) == 0
-            algo = _autotune(key, lib.crdr_conv2d_wgrad_num_configs(), 8, run, extra=_wgrad_wino4_ids(), result=lambda: tmp, agree=TUNE_AGREE["wgrad"])
-            d.accumulate = int(accumulate)
-        d.algo = _wa(algo)
-    nbytes = lib.crdr_conv2d_wgrad_workspace(C.byref(d))
-    e0 = _prof_begin()
-    if defer and WGRAD_DEFER is not None and WGRAD_DEFER.device == p.device:
-        job = L.WgradJob()
-        L.check(lib.crdr_conv2d_wgrad_partial(C.byref(d), p.data_ptr(), q.data_ptr(), g.data_ptr(), WGRAD_DEFER.alloc(nbytes),
-                                              nbytes, C.byref(job), _stream()), "conv2d_wgrad_partial")
-        WGRAD_DEFER.jobs.append(job)
-    else:
-        ws, ws_n = workspace(nbytes, p.device)
-        L.check(lib.crdr_conv2d_wgrad(C.byref(d), p.data_ptr(), q.data_ptr(), g.data_ptr(), ws, ws_n, _stream()), "conv2d_wgrad")
-    _prof_end("wgrad", 2.0 * n * ph * pw * g.shape[0] * g.shape[1] * k[0] * k[1], e0,
-              f"W {g.shape[0]}x{g.shape[1]} k{k[0]}s{stride} p{ph}x{pw}")
+    key = ("w", n, ph, pw, pc4, ldp, qh, qw, qc4, ldq, k, stride, pad, g.shape[0], g.shape[1]) + _mk()
+    _wgrad(lib, d, 1, [p.data_ptr()], [q.data_ptr()], [g.data_ptr()], key, p.device, whole=True, algo=algo,
+           defer=defer and WGRAD_DEFER is not None and WGRAD_DEFER.device == p.device,
+           flops=2.0 * n * ph * pw * g.shape[0] * g.shape[1] * k[0] * k[1], label=f"W {g.shape[0]}x{g.shape[1]} k{k[0]}s{stride} p{ph}x{pw}")
     return g
 
 
@@ -1003,6 +1088,25 @@ def view(buf: torch.Tensor, c0: int, c: int) -> V:
     return V(buf.data_ptr() + 4 * c0, buf.shape[-1], c)
 
 
+def _conv_ios(xs, wpacks, ys, biases=None, pres=None, masks=None, ress=None, vec2=None, scale=None, shift=None):
+    """ConvIO array of a grouped launch: xs / ys / pres / masks / ress lists of V, wpacks / biases lists of addresses, vec2 / scale /
+    shift addresses shared by the group"""
+    ios = (L.ConvIO * len(xs))()
+    for g, io in enumerate(ios):
+        io.x, io.w, io.y, io.vec2 = xs[g].ptr, wpacks[g], ys[g].ptr, vec2
+        if biases is not None:
+            io.bias = biases[g]
+        if pres is not None:
+            io.pre = pres[g].ptr
+        if masks is not None:
+            io.mask = masks[g].ptr
+        if ress is not None:
+            io.res = ress[g].ptr
+        if scale is not None:
+            io.scale, io.shift = scale, shift
+    return ios
+
+
 def conv_group(n: int, h: int, w: int, xs, wpacks, ys, oc: int, k: Tuple[int, int], pad: int, transposed: bool, *,
                wrows: int, wcols: int, biases=None, pres=None, masks=None, flags: int = 0, device=None, label: str = "",
                plan_as: Optional[int] = None):
@@ -1028,60 +1132,14 @@ def conv_group(n: int, h: int, w: int, xs, wpacks, ys, oc: int, k: Tuple[int, in
     d = L.ConvDesc(N=n, H=h, W=w, C=x0.c, OH=h, OW=w, OC=oc, kh=k[0], kw=k[1], stride=1, pad=pad, transposed=int(transposed),
                    ldx=x0.ld, ldy=y0.ld, wrows=wrows, wcols=wcols, flags=flags, ldres=y0.ld if self_res else 0, ldg=0, wlayout=0, reserved=0,
                    ldpre=pres[0].ld if pres is not None else 0, ldmask=masks[0].ld if masks is not None else 0)
-    ios = (L.ConvIO * G)()
-    for g in range(G):
-        io = ios[g]
-        io.x, io.w, io.y = xs[g].ptr, wpacks[g], ys[g].ptr
-        if biases is not None:
-            io.bias = biases[g]
-        if pres is not None:
-            io.pre = pres[g].ptr
-        if masks is not None:
-            io.mask = masks[g].ptr
-        if self_res:
-            io.res = ys[g].ptr
-    GP = plan_as if plan_as else G
-    if FORCED_CONV_ALGO:
-        d.reserved = FORCED_CONV_ALGO
-    elif _prefer_wino(d, G):
-        d.reserved = _prefer_wino(d, G)
-    elif AUTOTUNE and (GP == G or ("g", GP, n, h, w, d.C, oc, k, pad, int(transposed), d.ldx, d.ldy, flags, d.ldpre, d.ldmask, wrows, wcols) in _algo_cache):
-        key = ("g", GP, n, h, w, d.C, oc, k, pad, int(transposed), d.ldx, d.ldy, flags, d.ldpre, d.ldmask, wrows, wcols)
-        algo = _algo_cache.get(key)
-        if algo is None:
-            # trials run on scratch outputs with the same strides (timing runs would accumulate into live data; and the tuner
-            # compares every candidate's result with the baseline plan's on a tensor it owns)
-            span = (n * h * w - 1) * y0.ld + oc
-            scratch, reset = _tune_scratch(G * span + 64, device)
-            tio = (L.ConvIO * G)()
-            for g in range(G):
-                for f_, _ in L.ConvIO._fields_:
-                    setattr(tio[g], f_, getattr(ios[g], f_))
-                tio[g].y = scratch.data_ptr() + 4 * g * span
-                if pres is not None and pres[g].ptr == ys[g].ptr:
-                    tio[g].pre = tio[g].y
-                if self_res:
-                    tio[g].res = tio[g].y
-
-            def run(a):
-                d.reserved = a
-                nb = lib.crdr_conv2d_grouped_workspace(C.byref(d), G)
-                w_, wn_ = workspace(nb, device, conv=True) if nb else (None, 0)
-                return _tune_conv_launch(lib, d, tio, G, w_, wn_, device)
-            algo = _autotune(key, lib.crdr_conv2d_num_configs(), 4, run, extra=_stream_ids(), result=lambda: scratch, reset=reset,
-                             agree=TUNE_AGREE["conv"], penalty=lambda: _tune_w4_penalty[0])
-        d.reserved = algo
-    elif GP != G:
-        d.reserved = lib.crdr_conv2d_choose_algo(C.byref(d), GP)
-    _demote_if_misaligned(d, ios, G, bool(FORCED_CONV_ALGO))
-    nbytes = lib.crdr_conv2d_grouped_workspace(C.byref(d), G)
-    ws, ws_n = workspace(nbytes, device, conv=True) if nbytes else (None, 0)
-    e0 = _prof_begin()
-    L.check(_launch_conv(lib, d, ios, G, ws, ws_n, [ios[g].w for g in range(G)], device), "conv2d_grouped")
-    _prof_end("igemm", 2.0 * G * n * h * w * x0.c * oc * k[0] * k[1], e0,
-              f"{'T' if transposed else 'C'} {G}x {x0.c}->{oc} k{k[0]} in{h}x{w} f{flags} {label}",
-              4.0 * G * (n * h * w * x0.c + n * h * w * oc * (1 + (pres is not None) + (masks is not None) + bool(flags & L.EPI_ACCUM))
-                         + k[0] * k[1] * x0.c * oc))
+    ios = _conv_ios(xs, wpacks, ys, biases, pres, masks, ys if self_res else None)
+    GP = plan_as or G
+    key = ("g", GP, n, h, w, d.C, oc, k, pad, int(transposed), d.ldx, d.ldy, flags, d.ldpre, d.ldmask, wrows, wcols)
+    _conv(lib, d, ios, G, key, device, plan_as=GP,
+          flops=2.0 * G * n * h * w * x0.c * oc * k[0] * k[1],
+          label=f"{'T' if transposed else 'C'} {G}x {x0.c}->{oc} k{k[0]} in{h}x{w} f{flags} {label}",
+          nbytes=4.0 * G * (n * h * w * x0.c + n * h * w * oc * (1 + (pres is not None) + (masks is not None) + bool(flags & L.EPI_ACCUM))
+                            + k[0] * k[1] * x0.c * oc))
 
 
 def wgrad_group(n: int, h: int, w: int, ps, qs, gs, gi: int, gj: int, k: Tuple[int, int], pad: int, *, device, accumulate=True,
@@ -1095,44 +1153,11 @@ def wgrad_group(n: int, h: int, w: int, ps, qs, gs, gi: int, gj: int, k: Tuple[i
     p0, q0 = ps[0], qs[0]
     d = L.WgradDesc(N=n, PH=h, PW=w, PC=p0.c, ldp=p0.ld, QH=h, QW=w, QC=q0.c, ldq=q0.ld, kh=k[0], kw=k[1], stride=1, pad=pad,
                     gI=gi, gJ=gj, accumulate=int(accumulate), algo=_wa(0))
-    pa, qa, ga = (C.c_void_p * G)(*[v.ptr for v in ps]), (C.c_void_p * G)(*[v.ptr for v in qs]), (C.c_void_p * G)(*[g[0] for g in gs])
-    if AUTOTUNE:
-        key = ("wg", G, n, h, w, p0.c, p0.ld, q0.c, q0.ld, k, pad, gi, gj) + _mk()
-        algo = _algo_cache.get(key)
-        if algo is None:
-            tmp = torch.zeros(G * gi * gj * k[0] * k[1] + 64, dtype=torch.float32, device=device)
-            ta = (C.c_void_p * G)(*[tmp.data_ptr() + 4 * g * gi * gj * k[0] * k[1] for g in range(G)])
-            jobs_t = (L.WgradJob * G)()
-
-            slab = [0]
-
-            def run(a):
-                d.algo = _wa(a)
-                nb = lib.crdr_conv2d_wgrad_grouped_workspace(C.byref(d), G)
-                if nb == 0 or nb > (2 << 30):
-                    return False
-                slab[0] = nb
-                w_, wn_ = workspace(nb, device)
-                return lib.crdr_conv2d_wgrad_partial_grouped(C.byref(d), pa, qa, ta, G, w_, wn_, jobs_t, _stream()) == 0
-            # + the batched reduce's read of these slabs at its measured 3.8 TB/s (profiles/r2_h_hbm_families.json)
-            def finished():   # the trial's slabs reduced into tmp (the jobs accumulate: tmp is zeroed by reset())
-                reduce_jobs_now(jobs_t, device)
-                return tmp
-            algo = _autotune(key, lib.crdr_conv2d_wgrad_num_configs(), 8, run, extra=_wgrad_wino4_ids(), penalty=lambda: slab[0] / 3.8e9, result=finished,
-                             reset=tmp.zero_, agree=TUNE_AGREE["wgrad"])
-        d.algo = _wa(algo)
-    nbytes = lib.crdr_conv2d_wgrad_grouped_workspace(C.byref(d), G)
-    jobs = (L.WgradJob * G)()
-    e0 = _prof_begin()
-    assert WGRAD_DEFER is not None, "wgrad_group needs deferred weight-gradient reductions (ops.WGRAD_DEFER)"
-    L.check(lib.crdr_conv2d_wgrad_partial_grouped(C.byref(d), pa, qa, ga, G, WGRAD_DEFER.alloc(nbytes), nbytes, jobs, _stream()),
-            "conv2d_wgrad_partial_grouped")
-    for g in range(G):
-        jb = L.WgradJob()
-        C.memmove(C.byref(jb), C.byref(jobs[g]), C.sizeof(L.WgradJob))
-        jb.gJtot = gs[g][1]
-        WGRAD_DEFER.jobs.append(jb)
-    _prof_end("wgrad", 2.0 * G * n * h * w * gi * gj * k[0] * k[1], e0, f"W {G}x {gi}x{gj} k{k[0]} p{h}x{w} {label}")
+    key = ("wg", G, n, h, w, p0.c, p0.ld, q0.c, q0.ld, k, pad, gi, gj) + _mk()
+    jobs = _wgrad(lib, d, G, [v.ptr for v in ps], [v.ptr for v in qs], [g[0] for g in gs], key, device,
+                  flops=2.0 * G * n * h * w * gi * gj * k[0] * k[1], label=f"W {G}x {gi}x{gj} k{k[0]} p{h}x{w} {label}")
+    for jb, g in zip(jobs, gs):
+        jb.gJtot = g[1]
 
 
 def wgrad_split(n: int, h: int, w: int, p: V, q: V, parts, k: Tuple[int, int], pad: int, *, device, label: str = ""):
@@ -1142,35 +1167,16 @@ def wgrad_split(n: int, h: int, w: int, p: V, q: V, parts, k: Tuple[int, int], p
     lib = L.load()
     d = L.WgradDesc(N=n, PH=h, PW=w, PC=p.c, ldp=p.ld, QH=h, QW=w, QC=q.c, ldq=q.ld, kh=k[0], kw=k[1], stride=1, pad=pad,
                     gI=p.c, gJ=q.c, accumulate=1, algo=_wa(0))
-    if AUTOTUNE:
-        key = ("ws", n, h, w, p.c, p.ld, q.c, q.ld, k, pad) + _mk()
-        algo = _algo_cache.get(key)
-        if algo is None:
-            tmp = torch.zeros(p.c * q.c * k[0] * k[1], dtype=torch.float32, device=device)
-
-            def run(a):
-                d.algo, d.accumulate = _wa(a), 0
-                nb = lib.crdr_conv2d_wgrad_workspace(C.byref(d))
-                if nb == 0 or nb > (2 << 30):
-                    return False
-                w_, wn_ = workspace(nb, device)
-                return lib.crdr_conv2d_wgrad(C.byref(d), p.ptr, q.ptr, tmp.data_ptr(), w_, wn_, _stream()) == 0
-            algo = _autotune(key, lib.crdr_conv2d_wgrad_num_configs(), 8, run, extra=_wgrad_wino4_ids(), result=lambda: tmp, agree=TUNE_AGREE["wgrad"])
-            d.accumulate = 1
-        d.algo = _wa(algo)
-    nbytes = lib.crdr_conv2d_wgrad_workspace(C.byref(d))
-    job = L.WgradJob()
-    e0 = _prof_begin()
-    assert WGRAD_DEFER is not None
-    L.check(lib.crdr_conv2d_wgrad_partial(C.byref(d), p.ptr, q.ptr, parts[0][2], WGRAD_DEFER.alloc(nbytes), nbytes, C.byref(job),
-                                          _stream()), "conv2d_wgrad_partial")
+    key = ("ws", n, h, w, p.c, p.ld, q.c, q.ld, k, pad) + _mk()
+    job, = _wgrad(lib, d, 1, [p.ptr], [q.ptr], [parts[0][2]], key, device, whole=True,
+                  flops=2.0 * n * h * w * p.c * q.c * k[0] * k[1], label=f"W {p.c}x{q.c} k{k[0]} p{h}x{w} {label}")
+    split = []
     for row0, rows, gptr, gjtot in parts:
-        jb = L.WgradJob()
-        C.memmove(C.byref(jb), C.byref(job), C.sizeof(L.WgradJob))
+        jb = L.WgradJob.from_buffer_copy(job)
         jb.slab = job.slab + 4 * row0 * q.c
         jb.g, jb.gI, jb.gJtot = gptr, rows, gjtot
-        WGRAD_DEFER.jobs.append(jb)
-    _prof_end("wgrad", 2.0 * n * h * w * p.c * q.c * k[0] * k[1], e0, f"W {p.c}x{q.c} k{k[0]} p{h}x{w} {label}")
+        split.append(jb)
+    WGRAD_DEFER.jobs[-1:] = split   # (the slab's one job becomes one job per part)
 
 
 def colsum_scatter(x: V, m: int, block: int, outs_table: torch.Tensor, device, accumulate: bool = True):
@@ -1310,87 +1316,14 @@ def conv_multi(n: int, h: int, w: int, oh: int, ow: int, xs, wpacks, ys, oc: int
                    ldx=x0.ld, ldy=y0.ld, wrows=wrows, wcols=wcols, flags=flags, ldres=ress[0].ld if ress is not None else 0, ldg=0,
                    wlayout=wlayout, reserved=0, ldpre=pres[0].ld if pres is not None else 0,
                    ldmask=masks[0].ld if masks is not None else 0)
-    ios = (L.ConvIO * G)()
-    for g in range(G):
-        io = ios[g]
-        io.x, io.w, io.y = xs[g].ptr, wpacks[g], ys[g].ptr
-        if biases is not None:
-            io.bias = biases[g]
-        if pres is not None:
-            io.pre = pres[g].ptr
-        if masks is not None:
-            io.mask = masks[g].ptr
-        if ress is not None:
-            io.res = ress[g].ptr
-        if vec2 is not None:
-            io.vec2 = vec2
-        if scale is not None:
-            io.scale, io.shift = scale, shift
-    span = (n * oh * ow - 1) * y0.ld + oc
-
-    def cs_alloc(scratch_ok=False):
-        rows, ld = C.c_int(), C.c_int()
-        L.check(lib.crdr_conv2d_colsum_layout(C.byref(d), G, C.byref(rows), C.byref(ld)), "conv2d_colsum_layout")
-        nf = max(1, rows.value * 2 * ld.value)
-        if scratch_ok:  # tuner trial: any scratch will do
-            t = torch.empty(G * nf, dtype=torch.float32, device=device)
-            return [t.data_ptr() + 4 * g * nf for g in range(G)], rows.value, ld.value, t
-        q = colsum_queue(device)
-        return [q.alloc(nf) for _ in range(G)], rows.value, ld.value, None
-    if FORCED_CONV_ALGO:
-        d.reserved = FORCED_CONV_ALGO
-    elif _prefer_wino(d, G):
-        d.reserved = _prefer_wino(d, G)
-    elif AUTOTUNE:
-        key = ("m", G, n, h, w, oh, ow, d.C, oc, k, stride, pad, int(transposed), d.ldx, d.ldy, flags, d.ldres, d.ldpre, d.ldmask,
-               wrows, wcols, wlayout)
-        algo = _algo_cache.get(key)
-        if algo is None:
-            tio = (L.ConvIO * G)()
-            C.memmove(tio, ios, C.sizeof(ios))
-            # trials run on scratch outputs (timing runs must not accumulate into live data; the tuner compares every candidate's
-            # result with the baseline plan's on a tensor it owns)
-            scratch, reset = _tune_scratch(G * span + 64, device)
-            for g in range(G):
-                tio[g].y = scratch.data_ptr() + 4 * g * span
-                if pres is not None and pres[g].ptr == ys[g].ptr:
-                    tio[g].pre = tio[g].y
-                if ress is not None and ress[g].ptr == ys[g].ptr:
-                    tio[g].res = tio[g].y
-            keep = []
-
-            def run(a):
-                d.reserved = a
-                if colsum:
-                    try:
-                        bufs, _, _, t = cs_alloc(True)
-                    except L.CrdrHipError:
-                        return False
-                    keep[:] = [t]
-                    for g in range(G):
-                        tio[g].cs = bufs[g]
-                nb = lib.crdr_conv2d_grouped_workspace(C.byref(d), G)
-                w_, wn_ = workspace(nb, device, conv=True) if nb else (None, 0)
-                return _tune_conv_launch(lib, d, tio, G, w_, wn_, device)
-            algo = _autotune(key, lib.crdr_conv2d_num_configs(), 4, run, extra=_stream_ids(), result=lambda: scratch, reset=reset,
-                             agree=TUNE_AGREE["conv"], penalty=lambda: _tune_w4_penalty[0])
-        d.reserved = algo
-    _demote_if_misaligned(d, ios, G, bool(FORCED_CONV_ALGO))
-    out = None
-    if colsum:
-        bufs, rows, ld, _ = cs_alloc()
-        for g in range(G):
-            ios[g].cs = bufs[g]
-        out = [(b, rows, ld) for b in bufs]
-    nbytes = lib.crdr_conv2d_grouped_workspace(C.byref(d), G)
-    ws, ws_n = workspace(nbytes, device, conv=True) if nbytes else (None, 0)
-    e0 = _prof_begin()
-    L.check(_launch_conv(lib, d, ios, G, ws, ws_n, [ios[g].w for g in range(G)], device), "conv2d_grouped")
-    _prof_end("igemm", 2.0 * G * n * (h * w if transposed else oh * ow) * x0.c * oc * k[0] * k[1], e0,
-              f"{'T' if transposed else 'C'} {G}x {x0.c}->{oc} k{k[0]}s{stride} in{h}x{w} f{flags} {label}",
-              4.0 * G * (n * h * w * x0.c + n * oh * ow * oc * (1 + (pres is not None) + (masks is not None) + (ress is not None)
-                                                                 + bool(flags & L.EPI_ACCUM)) + k[0] * k[1] * x0.c * oc))
-    return out
+    ios = _conv_ios(xs, wpacks, ys, biases, pres, masks, ress, vec2, scale, shift)
+    key = ("m", G, n, h, w, oh, ow, d.C, oc, k, stride, pad, int(transposed), d.ldx, d.ldy, flags, d.ldres, d.ldpre, d.ldmask,
+           wrows, wcols, wlayout)
+    return _conv(lib, d, ios, G, key, device, colsum=colsum,
+                 flops=2.0 * G * n * (h * w if transposed else oh * ow) * x0.c * oc * k[0] * k[1],
+                 label=f"{'T' if transposed else 'C'} {G}x {x0.c}->{oc} k{k[0]}s{stride} in{h}x{w} f{flags} {label}",
+                 nbytes=4.0 * G * (n * h * w * x0.c + n * oh * ow * oc * (1 + (pres is not None) + (masks is not None) + (ress is not None)
+                                                                          + bool(flags & L.EPI_ACCUM)) + k[0] * k[1] * x0.c * oc))
 
 
 def wgrad_multi(n: int, ph: int, pw: int, qh: int, qw: int, ps, qs, gs, gi: int, gj: int, k: Tuple[int, int], stride: int, pad: int, *,
@@ -1403,40 +1336,6 @@ def wgrad_multi(n: int, ph: int, pw: int, qh: int, qw: int, ps, qs, gs, gi: int,
     pc, qc = min((p0.c + 3) // 4 * 4, p0.ld), min((q0.c + 3) // 4 * 4, q0.ld)
     d = L.WgradDesc(N=n, PH=ph, PW=pw, PC=pc, ldp=p0.ld, QH=qh, QW=qw, QC=qc, ldq=q0.ld, kh=k[0], kw=k[1], stride=stride, pad=pad,
                     gI=gi, gJ=gj, accumulate=1, algo=_wa(0))
-    pa, qa, ga = (C.c_void_p * G)(*[v.ptr for v in ps]), (C.c_void_p * G)(*[v.ptr for v in qs]), (C.c_void_p * G)(*gs)
-    if AUTOTUNE:
-        key = ("wm", G, n, ph, pw, pc, p0.ld, qh, qw, qc, q0.ld, k, stride, pad, gi, gj) + _mk()
-        algo = _algo_cache.get(key)
-        if algo is None:
-            tmp = torch.zeros(G * gi * gj * k[0] * k[1] + 64, dtype=torch.float32, device=device)
-            ta = (C.c_void_p * G)(*[tmp.data_ptr() + 4 * g * gi * gj * k[0] * k[1] for g in range(G)])
-            jobs_t = (L.WgradJob * G)()
-
-            slab = [0]
-
-            def run(a):
-                d.algo = _wa(a)
-                nb = lib.crdr_conv2d_wgrad_grouped_workspace(C.byref(d), G)
-                if nb == 0 or nb > (2 << 30):
-                    return False
-                slab[0] = nb
-                w_, wn_ = workspace(nb, device)
-                return lib.crdr_conv2d_wgrad_partial_grouped(C.byref(d), pa, qa, ta, G, w_, wn_, jobs_t, _stream()) == 0
-            # + the batched reduce's read of these slabs at its measured 3.8 TB/s (profiles/r2_h_hbm_families.json)
-            def finished():   # the trial's slabs reduced into tmp (the jobs accumulate: tmp is zeroed by reset())
-                reduce_jobs_now(jobs_t, device)
-                return tmp
-            algo = _autotune(key, lib.crdr_conv2d_wgrad_num_configs(), 8, run, extra=_wgrad_wino4_ids(), penalty=lambda: slab[0] / 3.8e9, result=finished,
-                             reset=tmp.zero_, agree=TUNE_AGREE["wgrad"])
-        d.algo = _wa(algo)
-    nbytes = lib.crdr_conv2d_wgrad_grouped_workspace(C.byref(d), G)
-    jobs = (L.WgradJob * G)()
-    e0 = _prof_begin()
-    assert WGRAD_DEFER is not None, "wgrad_multi needs deferred weight-gradient reductions (ops.WGRAD_DEFER)"
-    L.check(lib.crdr_conv2d_wgrad_partial_grouped(C.byref(d), pa, qa, ga, G, WGRAD_DEFER.alloc(nbytes), nbytes, jobs, _stream()),
-            "conv2d_wgrad_partial_grouped")
-    for g in range(G):
-        jb = L.WgradJob()
-        C.memmove(C.byref(jb), C.byref(jobs[g]), C.sizeof(L.WgradJob))
-        WGRAD_DEFER.jobs.append(jb)
-    _prof_end("wgrad", 2.0 * G * n * ph * pw * gi * gj * k[0] * k[1], e0, f"W {G}x {gi}x{gj} k{k[0]}s{stride} p{ph}x{pw} {label}")
+    key = ("wm", G, n, ph, pw, pc, p0.ld, qh, qw, qc, q0.ld, k, stride, pad, gi, gj) + _mk()
+    _wgrad(lib, d, G, [v.ptr for v in ps], [v.ptr for v in qs], gs, key, device,
+           flops=2.0 * G * n * ph * pw * gi * gj * k[0] * k[1], label=f"W {G}x {gi}x{gj} k{k[0]}s{stride} p{ph}x{pw} {label}")

@@ -481,6 +481,43 @@ def test_winograd_f4x4_epilogues_slices_groups_colsum():
         _close(y4[g].permute(0, 3, 1, 2), refg, f"grouped masked output {g} vs fp64", rtol=2e-5)
 
 
+def test_winograd_f4x4_tuned_plan_demoted_on_misaligned_output():
+    """a tuned F(4x4) plan is keyed by shape and strides, not by pointer alignment: a launch whose output view starts at a channel offset that
+    is not a multiple of 4 floats (the kernel's epilogue works with 16-byte accesses) runs the built-in plan instead, bit for bit"""
+    from crdr_amd.hip import lib as L
+    from crdr_amd.hip import ops
+    dev = _dev()
+    n, ci, h, w, co = 2, 64, 20, 72, 96
+    x = _rand(n, ci, h, w, seed=5).to(dev).contiguous(memory_format=torch.channels_last)
+    wp = ops.pack_weight(_rand(co, ci, 3, 3, seed=6, scale=(ci * 9) ** -0.5).to(dev), transpose=False)
+    b = _rand(co, seed=7).to(dev)
+    # the conv2d_raw tuner key of this launch: output pixel stride co + 8, output channels from offset 2 (8 bytes off 16-byte alignment)
+    key = ("c", n, h, w, ci, h, w, co, (3, 3), 1, 1, 0, ci, co + 8, L.EPI_BIAS, 0, 0, 0)
+
+    def run():
+        owide = torch.zeros(n, co + 8, h, w, device=dev).contiguous(memory_format=torch.channels_last)
+        ops.conv2d_raw(x, wp, co, (3, 3), 1, 1, False, (h, w), bias=b, flags=L.EPI_BIAS, out=owide[:, 2:2 + co])
+        torch.cuda.synchronize()
+        return owide
+
+    def refuse(k, *a, **kw):
+        raise AssertionError(f"the launch missed its preloaded tuner key: {k}")
+    keep = (ops.AUTOTUNE, dict(ops._algo_cache), ops._autotune)
+    try:
+        ops.AUTOTUNE = False
+        builtin = run()
+        ops.AUTOTUNE, ops._autotune = True, refuse
+        ops._algo_cache[key] = _wino_id() + 2
+        before = ops.WINO4_DEMOTED[0]
+        demoted = run()
+        assert ops.WINO4_DEMOTED[0] == before + 1
+    finally:
+        ops.AUTOTUNE, ops._autotune = keep[0], keep[2]
+        ops._algo_cache.clear()
+        ops._algo_cache.update(keep[1])
+    assert torch.equal(demoted, builtin)
+
+
 def test_winograd_rejects_other_shapes():
     from crdr_amd.hip import lib as L
     from crdr_amd.hip import ops
