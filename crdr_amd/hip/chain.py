@@ -15,6 +15,7 @@ output -- is ONE autograd node whose backward is written out:
 The forward issues exactly the launches the per-layer path issued (same kernels, same packs), so values are unchanged."""
 from __future__ import annotations
 
+import itertools
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -41,6 +42,9 @@ class Unit:
         self.layers, self.residual = list(layers), residual
 
 
+_chain_sites = itertools.count()
+
+
 class ChainSpec:
     """Static description: `groups` parallel chains (lists of units) of identical geometry; `affine` = the last conv of
     group 0's last unit carries a per-channel scale + shift epilogue (InterpChAtt); nvec = number of beta vectors."""
@@ -53,6 +57,9 @@ class ChainSpec:
         self.affine, self.nvec, self.name = affine, nvec, name
         assert not (affine and self.G > 1)
         self._dv = None
+        # the flush site of this chain's column sums: never reused, unlike id(self) -- the tables of a site that a HIP graph captured stay
+        # frozen (hip/batched.py), and a later chain must not inherit those of a dead one
+        self.site = ("chain", next(_chain_sites))
 
     def unit(self, g, u) -> Unit:
         return self.groups[g][u]
@@ -315,7 +322,7 @@ class _ChainFn(torch.autograd.Function):
                     dz_v, dz_t, dz_hw = ys, yts, (ih, iw)
                 if u == 0 and dx_out is None and ctx.needs_input_grad[0]:
                     dx_out = dz_t
-            q.flush(("chain", id(spec)))
+            q.flush(spec.site)
             if local:
                 ops.WGRAD_DEFER.flush(("chain-local", dev.index))
         finally:

@@ -184,47 +184,26 @@ class PackTable:
     """The packs whose parameter lives in one address range (an optimiser's flat buffer, or a partition of it), refilled
     by ONE launch right after that optimiser's update -- instead of one small launch per layer on next use.
 
-    The device-side table has a fixed capacity and is rewritten in place when new packs appear, so a HIP graph that
-    captured the launch keeps covering everything."""
+    Its batched.JobTable is rewritten in place when new packs appear, also under a graph that replays it
+    (frozen_after_capture=False, see batched): the captured launch keeps covering everything."""
     CAP = 4096
-    ITEM = 56  # sizeof(crdr_pack_item)
 
     def __init__(self, flat: torch.Tensor, lo: int = 0, hi: Optional[int] = None):
         hi = flat.numel() if hi is None else hi
         self.lo, self.hi = flat.data_ptr() + 4 * lo, flat.data_ptr() + 4 * hi
         self.device = flat.device
-        self.items = torch.zeros(self.CAP * self.ITEM, dtype=torch.uint8, device=flat.device)
-        self.prefix = torch.zeros(self.CAP + 1, dtype=torch.int64, device=flat.device)
-        self.meta = torch.zeros(2, dtype=torch.int64, device=flat.device)
+        self.table = ops.JobTable(flat.device, L.PackItem, self.CAP, name="PackTable")
         self.entries, self.singles = [], []
         self.filters = None
         self._seen = -1
 
     def _refresh(self) -> None:
-        import numpy as np
         if self._seen == _pack_serial:
             return
         mine = [e for e in _pack_entries if self.lo <= e.weight.data_ptr() < self.hi and e.dst.device == self.device]
         ents = [e for e in mine if e.mode in (0, 1) and e.T <= 32]   # what the batched kernel takes
-        self.singles = [e for e in mine if not (e.mode in (0, 1) and e.T <= 32)]
-        if [id(e) for e in ents] != [id(e) for e in self.entries]:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("PackTable: new weight packs appeared during graph capture (run eager warm-up iterations first)")
-            assert len(ents) <= self.CAP
-            rec = np.zeros(len(ents), dtype=np.dtype([("src", "<u8"), ("dst", "<u8"), ("I", "<i4"), ("J", "<i4"), ("T", "<i4"),
-                                                        ("rows", "<i4"), ("cols", "<i4"), ("mode", "<i4"), ("srcJ", "<i4"),
-                                                        ("dld", "<i4"), ("tstride", "<i8")]))
-            pre = np.zeros(len(ents) + 1, dtype=np.int64)
-            for k, e in enumerate(ents):
-                rec[k] = (e.weight.data_ptr() + e.src_off, e.dst.data_ptr() + e.dst_off, e.I, e.J, e.T, e.rows, e.cols, e.mode,
-                          e.srcJ, e.dld, e.tstride)
-                pre[k + 1] = pre[k] + (e.rows // 8) * (e.cols // 32)
-            assert rec.dtype.itemsize == self.ITEM
-            if len(ents):
-                self.items[:len(ents) * self.ITEM].copy_(torch.from_numpy(rec.view(np.uint8).copy()))
-            self.prefix[:len(ents) + 1].copy_(torch.from_numpy(pre))
-            self.meta.copy_(torch.tensor([len(ents), int(pre[-1])], dtype=torch.int64))
-            self.entries = ents
+        self.table.upload([e.item() for e in ents], lambda it: (it.rows // 8) * (it.cols // 32))
+        self.entries, self.singles = ents, [e for e in mine if not (e.mode in (0, 1) and e.T <= 32)]
         self._seen = _pack_serial
 
     def refill(self) -> None:
@@ -234,8 +213,7 @@ class PackTable:
             ops.bump_pack_version(ptr)
         if self.entries:
             lib = L.load()
-            L.check(lib.crdr_pack_weights_batched(self.items.data_ptr(), self.prefix.data_ptr(), self.meta.data_ptr(),
-                                                  ops._stream()), "pack_weights_batched")
+            L.check(lib.crdr_pack_weights_batched(*self.table.operands, ops._stream()), "pack_weights_batched")
         for e in self.singles:
             e.fill()
         for e in self.entries + self.singles:

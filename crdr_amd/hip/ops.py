@@ -12,6 +12,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import lib as L
+from .batched import BumpArena, JobTable, SiteTables  # noqa: F401  (the capture rules of the batched launches live there)
 
 _ws_cache = {}
 _ws_keep = []   # superseded buffers stay alive: captured graphs may still reference them
@@ -254,16 +255,13 @@ class filter_scope:
 
 
 class FilterTable:
-    """The filter caches derived from a set of weight packs (an optimiser's), rebuilt by one launch: device-side item table of fixed
-    capacity, rewritten in place when new caches appear, so a HIP graph that captured the launch keeps covering everything."""
+    """The filter caches derived from a set of weight packs (an optimiser's), rebuilt by one launch.  Its batched.JobTable is rewritten in place
+    when new caches appear, also under a graph that replays it (frozen_after_capture=False): the captured launch keeps covering everything."""
     CAP = 1024
-    ITEM = C.sizeof(L.W4FilterItem)
 
     def __init__(self, device):
         self.device = device
-        self.items = torch.zeros(self.CAP * self.ITEM, dtype=torch.uint8, device=device)
-        self.prefix = torch.zeros(self.CAP + 1, dtype=torch.int64, device=device)
-        self.meta = torch.zeros(2, dtype=torch.int64, device=device)
+        self.table = JobTable(device, L.W4FilterItem, self.CAP, name="FilterTable")
         self.entries = []
         self._seen = -1
         self._packs = frozenset()
@@ -278,18 +276,8 @@ class FilterTable:
         if len(ents) > self.CAP:   # more caches than the device table holds: the most recently used stay in the batched rebuild, the others
             ents = sorted(ents, key=lambda e: -e.tick)[:self.CAP]   # fall behind their packs' versions and re-transform inside their launches
             ents.sort(key=lambda e: e.tick)
-        if [id(e) for e in ents] != [id(e) for e in self.entries]:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("FilterTable: new filter caches appeared during graph capture (run eager warm-up iterations first)")
-            raw, pre = bytearray(), [0]
-            for e in ents:
-                raw += bytes(e.item)
-                pre.append(pre[-1] + int(e.item.units))
-            if ents:
-                self.items[:len(raw)].copy_(torch.frombuffer(raw, dtype=torch.uint8))
-            self.prefix[:len(pre)].copy_(torch.tensor(pre, dtype=torch.int64))
-            self.meta.copy_(torch.tensor([len(ents), pre[-1]], dtype=torch.int64))
-            self.entries = ents
+        self.table.upload([e.item for e in ents], lambda it: int(it.units))
+        self.entries = ents
         self._seen, self._packs = _filter_serial[0], pack_ptrs
 
     def refill(self, pack_ptrs) -> None:
@@ -297,7 +285,7 @@ class FilterTable:
         self._refresh(pack_ptrs)
         if self.entries:
             lib = L.load()
-            L.check(lib.crdr_w4_filters_batched(self.items.data_ptr(), self.prefix.data_ptr(), self.meta.data_ptr(), _stream()), "w4_filters_batched")
+            L.check(lib.crdr_w4_filters_batched(*self.table.operands, _stream()), "w4_filters_batched")
             FILTER_SCOPE_STATS["batched"] += len(self.entries)
             for e in self.entries:
                 e.versions = tuple(pack_version(p_) for p_ in e.wkeys)
@@ -887,53 +875,29 @@ def conv2d_wgrad_raw(p: torch.Tensor, q: torch.Tensor, g: torch.Tensor, k, strid
 
 
 class DeferredWgrad:
-    """Weight-gradient reductions of a whole backward pass finished by ONE launch (crdr_wgrad_reduce_batched) instead of
-    one small launch per layer.  Slabs are bump-allocated from an arena that is recycled at every flush; the device-side
-    job tables are kept per flush site and rewritten only when their content changes, so a site captured in a HIP graph
-    (same layers, same buffers every iteration) replays without host work."""
+    """Weight-gradient reductions of a whole backward pass finished by ONE launch (crdr_wgrad_reduce_batched) instead of one small launch
+    per layer.  Slabs come from a batched.BumpArena recycled at every flush, the job tables are batched.SiteTables, one pair per flush site
+    and round: a site captured in a HIP graph (same layers, same buffers every iteration) replays without host work (rules: see batched)."""
     CAP = 4096
 
     def __init__(self, device, arena_bytes: int = 2 << 30):
         self.device = torch.device(device)
-        self.arena = torch.empty(arena_bytes, dtype=torch.uint8, device=self.device)
-        self._keep = []
-        self.off = 0
-        self.cycle = 0  # bytes handed out since the last flush (over all arenas)
+        self._arena = BumpArena(self.device, arena_bytes, "DeferredWgrad: arena")
+        self.alloc = self._arena.alloc
         self.jobs = []
-        self.tables = {}
-        self._pinned = []  # arenas whose addresses are baked into captured graphs: never released
-
-    def _retire(self) -> None:
-        """The current arena is being replaced.  Slab addresses handed out during a capture live on in the graph's kernel
-        arguments, so an arena that was current during any capture stays allocated for the life of the process."""
-        (self._pinned if getattr(self, "_captured", False) else self._keep).append(self.arena)
-
-    def alloc(self, nbytes: int) -> int:
-        nbytes = (nbytes + 255) // 256 * 256
-        if torch.cuda.is_current_stream_capturing():
-            self._captured = True
-        if self.off + nbytes > self.arena.numel():
-            if torch.cuda.is_current_stream_capturing():
-                raise L.CrdrHipError("DeferredWgrad: arena too small during graph capture (run eager warm-up iterations first)")
-            self._retire()  # pending jobs still point into it
-            # big enough for a whole cycle like this one, so that the next iteration never grows again
-            self.arena = torch.empty(max(2 * self.arena.numel(), 2 * (self.cycle + nbytes)), dtype=torch.uint8, device=self.device)
-            self.off = 0
-        p = self.arena.data_ptr() + self.off
-        self.off += nbytes
-        self.cycle += nbytes
-        return p
+        self.tables = SiteTables(self.device, L.WgradJob, self.CAP, name="DeferredWgrad")
 
     def pending(self) -> int:
         return len(self.jobs)
 
-    def flush(self, key=None, twin=None) -> None:
-        """Reduce everything pending.  `twin` (eager calls only): a second table key that receives the same content, so
-        that a later graph capture of the same site -- which cannot upload -- finds its own, identical table."""
+    def drop(self) -> None:   # forget the pending jobs (an exception left them behind) and hand their slabs out again
+        self.jobs = []
+        self._arena.rewind()
+
+    def flush(self, key=None) -> None:
+        """Reduce everything pending; `key` names the flush site."""
         if not self.jobs:
             return
-        import numpy as np
-        lib = L.load()
         rounds = []  # no two jobs of one launch may write the same gradient (a weight used twice in one backward)
         for jb in self.jobs:
             for r in rounds:
@@ -943,50 +907,10 @@ class DeferredWgrad:
             else:
                 rounds.append(([jb], {jb.g}))
         for ri, (js, _) in enumerate(rounds):
-            assert len(js) <= self.CAP
-            host = b"".join(bytes(j) for j in js)
-            pre = np.zeros(len(js) + 1, dtype=np.int64)
-            for k, j in enumerate(js):
-                pre[k + 1] = pre[k] + _wgrad_job_tiles(j)
-            for tk in ([twin] if twin is not None and not torch.cuda.is_current_stream_capturing() else []):
-                self._table((tk, ri), host, pre, len(js))
-            tb = self._table((key, ri), host, pre, len(js))
-            L.check(lib.crdr_wgrad_reduce_batched(tb["jobs"].data_ptr(), tb["prefix"].data_ptr(), tb["meta"].data_ptr(),
-                                                  _stream()), "wgrad_reduce_batched")
+            tb = self.tables.upload((key, ri), js, _wgrad_job_tiles)
+            L.check(L.load().crdr_wgrad_reduce_batched(*tb.operands, _stream()), "wgrad_reduce_batched")
         self.jobs = []
-        self.off = 0
-        if not torch.cuda.is_current_stream_capturing():
-            if self.arena.numel() < self.cycle:  # the cycle spilled over several arenas: make the next one fit in one
-                self._retire()                   # (the reduce just launched may still be reading it: freed next flush)
-                self.arena = torch.empty(2 * self.cycle, dtype=torch.uint8, device=self.device)
-            else:
-                self._keep = []
-        self.cycle = 0
-
-    def _table(self, tkey, host: bytes, pre, njobs: int):
-        """Device-side job table `tkey` holding `host` (uploaded only when the content changed)."""
-        tb = self.tables.get(tkey)
-        if tb is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise L.CrdrHipError("DeferredWgrad: first flush of this site happened during graph capture")
-            tb = self.tables[tkey] = {
-                "jobs": torch.zeros(self.CAP * C.sizeof(L.WgradJob), dtype=torch.uint8, device=self.device),
-                "prefix": torch.zeros(self.CAP + 1, dtype=torch.int64, device=self.device),
-                "meta": torch.zeros(2, dtype=torch.int64, device=self.device), "host": None}
-        if torch.cuda.is_current_stream_capturing():
-            tb["captured"] = True
-        if tb["host"] != host:
-            if torch.cuda.is_current_stream_capturing():
-                raise L.CrdrHipError("DeferredWgrad: the job table of a captured site changed")
-            if tb.get("captured"):
-                # a graph replays this table together with kernels that write the slab addresses it held at capture time
-                raise L.CrdrHipError("DeferredWgrad: an eager flush would rewrite the job table of a site captured in a HIP "
-                                     "graph (shapes or slab addresses changed since the capture): re-capture the graphs")
-            tb["jobs"][:len(host)].copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
-            tb["prefix"][:njobs + 1].copy_(torch.from_numpy(pre))
-            tb["meta"].copy_(torch.tensor([njobs, int(pre[-1])], dtype=torch.int64))
-            tb["host"] = host
-        return tb
+        self._arena.reset()
 
 
 def _wgrad_job_tiles(j) -> int:
@@ -997,25 +921,17 @@ def _wgrad_job_tiles(j) -> int:
 def reduce_jobs_now(jobs, device) -> None:
     """One crdr_wgrad_reduce_batched launch over `jobs` (a ctypes array / list of WgradJob) with a throw-away device table: the
     tuner finishes a trial's partial slabs with it so that the candidate's weight gradient can be compared with the baseline's."""
-    import numpy as np
-    js = list(jobs)
-    host = b"".join(bytes(j) for j in js)
-    pre = np.zeros(len(js) + 1, dtype=np.int64)
-    for k, j in enumerate(js):
-        pre[k + 1] = pre[k] + _wgrad_job_tiles(j)
-    tj = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(device)
-    tp = torch.from_numpy(pre).to(device)
-    tm = torch.tensor([len(js), int(pre[-1])], dtype=torch.int64).to(device)
-    L.check(L.load().crdr_wgrad_reduce_batched(tj.data_ptr(), tp.data_ptr(), tm.data_ptr(), _stream()), "wgrad_reduce_batched")
+    tb = JobTable(device, L.WgradJob, len(jobs), name="reduce_jobs_now").upload(jobs, _wgrad_job_tiles)
+    L.check(L.load().crdr_wgrad_reduce_batched(*tb.operands, _stream()), "wgrad_reduce_batched")
     torch.cuda.current_stream().synchronize()   # (the table dies with this frame)
 
 
 WGRAD_DEFER: Optional[DeferredWgrad] = None  # set by a trainer; every backward must then be followed by flush_wgrads()
 
 
-def flush_wgrads(key=None, twin=None) -> None:
+def flush_wgrads(key=None) -> None:
     if WGRAD_DEFER is not None:
-        WGRAD_DEFER.flush(key, twin)
+        WGRAD_DEFER.flush(key)
 
 
 def pending_wgrads() -> int:
@@ -1192,33 +1108,23 @@ def colsum_scatter(x: V, m: int, block: int, outs_table: torch.Tensor, device, a
 # general pointer-level conv launch (any stride / transposed / group size / epilogue) + in-epilogue column sums
 # ---------------------------------------------------------------------------------------------------------
 class ColsumQueue:
-    """Pending CRDR_EPI_COLSUM reductions of one device, finished by ONE crdr_colsum_finish_batched launch per flush.
-    The partial-sum buffers are bump-allocated from an arena that is recycled at every flush, so a flush site sees the
-    same addresses every iteration and its device-side job table -- kept per site, rewritten only when the content
-    changes -- survives HIP-graph capture (same scheme as DeferredWgrad)."""
+    """Pending CRDR_EPI_COLSUM reductions of one device, finished by ONE crdr_colsum_finish_batched launch per flush.  Same scheme as
+    DeferredWgrad (rules: see batched): partial rows from a BumpArena recycled at every flush, SiteTables per flush site; the pass-A scratch
+    is offset-addressed and its address is the tables' trailer (a captured finish launch carries it as a kernel argument)."""
     CAP = 512
 
     def __init__(self, device, arena_bytes: int = 128 << 20):
         self.device = torch.device(device)
-        self.arena = torch.empty(arena_bytes, dtype=torch.uint8, device=self.device)
-        self._old = []
-        self.off = 0
-        self.jobs = []
-        self.tables = {}
+        self._arena = BumpArena(self.device, arena_bytes, "ColsumQueue: arena")
+        self._scratch = BumpArena(self.device, 16 << 20, "ColsumQueue: scratch")
         self.scratch_off = 0   # floats of pass-A scratch handed out since the last flush
-        self.scratch = torch.empty(4 << 20, dtype=torch.float32, device=self.device)
+        self.jobs = []
+        self.tables = SiteTables(self.device, L.ColsumJob, self.CAP, rows=2, name="ColsumQueue")
+
+    arena = property(lambda self: self._arena.tensor)   # the uint8 tensor that the partial rows handed out since the last growth live in
 
     def alloc(self, nfloats: int) -> int:
-        nbytes = (4 * nfloats + 255) // 256 * 256
-        if self.off + nbytes > self.arena.numel():
-            if torch.cuda.is_current_stream_capturing():
-                raise L.CrdrHipError("ColsumQueue: arena too small during graph capture (run eager warm-up iterations first)")
-            self._old.append(self.arena)
-            self.arena = torch.empty(max(2 * self.arena.numel(), 4 * nbytes), dtype=torch.uint8, device=self.device)
-            self.off = 0
-        p = self.arena.data_ptr() + self.off
-        self.off += nbytes
-        return p
+        return self._arena.alloc(4 * nfloats)
 
     def add(self, cs_ptr: int, rows: int, ld: int, c: int, out_pre: Optional[int], out_post: Optional[int], accumulate: bool):
         slab = L.load().crdr_colsum_slab_rows()
@@ -1228,54 +1134,19 @@ class ColsumQueue:
         self.jobs.append(L.ColsumJob(cs=cs_ptr, out_pre=out_pre, out_post=out_post, rows=rows, ld=ld, C=c, accumulate=int(accumulate),
                                      nslab=nslab, cpad=cpad, scratch_off=off))
 
-    def _table(self, tkey, host, pre, njobs, cap):
-        tb = self.tables.get(tkey)
-        if tb is None:
-            if cap:
-                raise L.CrdrHipError("ColsumQueue: first flush of this site happened during graph capture")
-            tb = self.tables[tkey] = {"jobs": torch.zeros(self.CAP * C.sizeof(L.ColsumJob), dtype=torch.uint8, device=self.device),
-                                      "prefix": torch.zeros(2 * (self.CAP + 1), dtype=torch.int64, device=self.device),
-                                      "meta": torch.zeros(3, dtype=torch.int64, device=self.device), "host": None}
-        if tb["host"] != host:
-            if cap:
-                raise L.CrdrHipError("ColsumQueue: the job table of a captured site changed")
-            tb["jobs"][:len(host)].copy_(torch.frombuffer(bytearray(host), dtype=torch.uint8))
-            tb["prefix"][:pre.size].copy_(torch.from_numpy(pre.reshape(-1)))
-            tb["meta"].copy_(torch.tensor([njobs, int(pre[0, njobs]), int(pre[1, njobs])], dtype=torch.int64))
-            tb["host"] = host
-        return tb
+    def drop(self) -> None:   # forget the pending jobs and hand their partial rows out again
+        self.jobs, self.scratch_off = [], 0
+        self._arena.rewind()
 
     def flush(self, key) -> None:
-        if not self.jobs:
-            self.off = 0
-            self.scratch_off = 0
-            return
-        import numpy as np
-        lib = L.load()
-        js = self.jobs
-        assert len(js) <= self.CAP
-        cap = torch.cuda.is_current_stream_capturing()
-        if self.scratch_off > self.scratch.numel():
-            if cap:
-                raise L.CrdrHipError("ColsumQueue: scratch too small during graph capture (run eager warm-up iterations first)")
-            self._old.append(self.scratch)
-            self.scratch = torch.empty(2 * self.scratch_off, dtype=torch.float32, device=self.device)
-        host = b"".join(bytes(j) for j in js) + self.scratch.data_ptr().to_bytes(8, "little")
-        pre = np.zeros((2, self.CAP + 1), dtype=np.int64)   # row 0: pass-A tiles, row 1: pass-B tiles
-        for k, j in enumerate(js):
-            pre[0, k + 1] = pre[0, k] + (j.cpad // 64) * j.nslab
-            pre[1, k + 1] = pre[1, k] + j.cpad // 64
-        if not cap:  # the twin a later capture of this site will find (it cannot upload)
-            self._table((key, True), host, pre, len(js), False)
-        tb = self._table((key, cap), host, pre, len(js), cap)
-        L.check(lib.crdr_colsum_finish_batched(tb["jobs"].data_ptr(), tb["prefix"].data_ptr(),
-                                               tb["prefix"].data_ptr() + 8 * (self.CAP + 1), tb["meta"].data_ptr(),
-                                               self.scratch.data_ptr(), _stream()), "colsum_finish_batched")
-        self.jobs = []
-        self.off = 0
-        self.scratch_off = 0
-        if not cap and self._old:
-            self._old = self._old[-1:]  # (the launch just issued may still read the previous arena)
+        if self.jobs:
+            scratch = self._scratch.reserve(4 * self.scratch_off)
+            tb = self.tables.upload(key, self.jobs, lambda j: ((j.cpad // 64) * j.nslab, j.cpad // 64),   # pass-A tiles, pass-B tiles
+                                    trailer=scratch.to_bytes(8, "little"))
+            L.check(L.load().crdr_colsum_finish_batched(*tb.operands, scratch, _stream()), "colsum_finish_batched")
+        self.jobs, self.scratch_off = [], 0
+        self._arena.reset()
+        self._scratch.reset()
 
 
 _colsum_queues = {}

@@ -188,10 +188,7 @@ class BaseTrainer:
 
     def _flush_wgrads(self, site: str) -> None:
         from crdr_amd.hip import ops as _ops
-        # captured and eager executions of a site keep separate job tables: an eager iteration after the capture (e.g. the
-        # profiling steps of bench.py) must not rewrite the table a graph replays with
-        cap = torch.cuda.is_current_stream_capturing()
-        _ops.flush_wgrads((site, self._flush_key, cap), twin=None if cap else (site, self._flush_key, True))
+        _ops.flush_wgrads((site, self._flush_key))   # (eager and captured executions of a site keep separate job tables: hip/batched.py)
 
     def _step_scope(self):
         """Context of one optimize_parameters call: the trainer's stream (graphs.step_scope) + deferred weight-gradient
@@ -267,6 +264,6 @@ class _TrainerStepScope:
             return self.inner.__exit__(*a)
         finally:
             if a[0] is not None and _ops.WGRAD_DEFER is not None:
-                _ops.WGRAD_DEFER.jobs, _ops.WGRAD_DEFER.off = [], 0  # an exception left reductions behind: drop them
+                _ops.WGRAD_DEFER.drop()  # an exception left reductions behind
             _ops.WGRAD_DEFER = self.prev
             _ops.MATRIX_BF16X3, _ops.MATRIX_BF16X6 = self.prev_mm

@@ -498,3 +498,160 @@ def test_merge_tune_db_keeps_the_winograd_class(tmp_path):
     out = json.load(open(o))["algos"]
     assert out == {"('c', 1)": 12 | (2 << 8), "('c', 2)": 38, "('m', 3)": 7, "('g', 4)": 36 | (1 << 8), "('w', 5)": 3, "('wm', 6)": 25, "('ws', 7)": 11}, out
     assert "2 entries re-timed, 5 kept" in r.stdout, r.stdout
+
+
+def _wjob(k):
+    from crdr_amd.hip import lib as L
+    return L.WgradJob(slab=4096 * k, g=1 << (20 + k), PC=32, QC=64, gI=3 + k, gJ=65, T=9, nsplit=2, accumulate=1, gJtot=65)
+
+
+def test_job_table_uploads_only_what_changed():
+    """batched.JobTable on host tensors: an unchanged upload is skipped, a changed one goes through; more items than the capacity are refused
+    and exactly the capacity plus a trailer is accepted (the trailer is compared, never copied); prefix rows and meta against a hand-computed
+    example for a one-row and a two-row table."""
+    from crdr_amd.hip import batched as B
+    from crdr_amd.hip import lib as L
+    from crdr_amd.hip import ops
+    size = ctypes.sizeof(L.WgradJob)
+    asked = []
+
+    def tiles(j):
+        asked.append(1)
+        return ops._wgrad_job_tiles(j)
+    tb = B.JobTable("cpu", L.WgradJob, 3)
+    assert tb.items.numel() == 3 * size and tb.prefix.shape == (1, 4) and tb.meta.numel() == 2 and len(tb.operands) == 3
+    jobs = [_wjob(0), _wjob(1)]
+    assert [ops._wgrad_job_tiles(j) for j in jobs] == [3 * 2, 4 * 2]   # gI x ceil(65 / 64)
+    assert tb.upload(jobs, tiles) is tb and len(asked) == 2
+    assert bytes(tb.items[:2 * size].numpy()) == bytes(jobs[0]) + bytes(jobs[1])
+    assert tb.prefix.tolist() == [[0, 6, 14, 0]] and tb.meta.tolist() == [2, 14]
+    tb.items[0] += 1                                          # (a mark that a rewrite would wipe)
+    tb.upload([_wjob(0), _wjob(1)], tiles)                    # equal bytes: nothing is asked of `tiles`, nothing is copied
+    assert len(asked) == 2 and tb.items[0] == bytes(jobs[0])[0] + 1
+    jobs[1].g += 256
+    tb.upload(jobs, tiles)
+    assert len(asked) == 4 and bytes(tb.items[:2 * size].numpy()) == bytes(jobs[0]) + bytes(jobs[1])
+    tb.upload(jobs[:1], tiles)                                # fewer items: the prefix behind them is zero again
+    assert tb.prefix.tolist() == [[0, 6, 0, 0]] and tb.meta.tolist() == [1, 6]
+    with pytest.raises(L.CrdrHipError, match="4 items, the device table holds 3"):
+        tb.upload([_wjob(k) for k in range(4)], tiles)
+    assert tb.meta.tolist() == [1, 6]
+    # two prefix rows (the column-sum finish: pass-A tiles, pass-B tiles), a full table and a trailer
+    cj = [L.ColsumJob(cs=256 * k, rows=40, ld=128, C=100 + k, accumulate=1, nslab=2 + k, cpad=128, scratch_off=1000 * k) for k in range(4)]
+    del asked[:]
+
+    def tiles2(j):
+        asked.append(2)
+        return (j.cpad // 64) * j.nslab, j.cpad // 64
+    t2 = B.JobTable("cpu", L.ColsumJob, 4, rows=2, frozen_after_capture=True)
+    t2.upload(cj, tiles2, trailer=b"\x01" * 8)
+    assert t2.items.numel() == 4 * ctypes.sizeof(L.ColsumJob) and bytes(t2.items.numpy()) == b"".join(bytes(j) for j in cj)
+    assert t2.prefix.tolist() == [[0, 4, 10, 18, 28], [0, 2, 4, 6, 8]] and t2.meta.tolist() == [4, 28, 8]
+    assert t2.operands[2] - t2.operands[1] == 8 * 5 and len(t2.operands) == 4
+    t2.upload(cj, tiles2, trailer=b"\x01" * 8)
+    assert len(asked) == 4
+    t2.upload(cj, tiles2, trailer=b"\x02" * 8)                # only the trailer moved: that counts as a change
+    assert len(asked) == 8
+    assert B.prefix_sums([]).tolist() == [[0]] and B.prefix_sums([2, 3, 4]).tolist() == [[0, 2, 5, 9]]
+    assert B.prefix_sums([(1, 10), (2, 20)], rows=2, width=4).tolist() == [[0, 1, 3, 0], [0, 10, 30, 0]]
+
+
+def test_job_table_capture_rules(monkeypatch):
+    """The rules of batched's docstring, with the capture state stubbed: a table created or changed under capture raises; a table used
+    under capture is replayed, and then only a table that is not frozen_after_capture may be rewritten eagerly; SiteTables keeps eager
+    and captured tables apart and fills the captured one while the site runs eagerly."""
+    from crdr_amd.hip import batched as B
+    from crdr_amd.hip import lib as L
+    from crdr_amd.hip import ops
+    cap = [False]
+    monkeypatch.setattr(B, "_capturing", lambda: cap[0])
+    tiles = ops._wgrad_job_tiles
+    a, b = [_wjob(0), _wjob(1)], [_wjob(0), _wjob(2)]
+    for frozen in (False, True):
+        tb = B.JobTable("cpu", L.WgradJob, 8, frozen_after_capture=frozen, name="T")
+        tb.upload(a, tiles)
+        cap[0] = True
+        with pytest.raises(L.CrdrHipError, match="T: the table changed during graph capture .run eager warm-up iterations first"):
+            tb.upload(b, tiles)
+        assert not tb.replayed and tb.meta.tolist() == [2, 14]
+        tb.upload(a, tiles)
+        assert tb.replayed
+        cap[0] = False
+        tb.upload(a, tiles)                                   # an eager pass with the same content leaves it alone
+        if frozen:
+            with pytest.raises(L.CrdrHipError, match="re-capture the graphs"):
+                tb.upload(b, tiles)
+            assert tb.meta.tolist() == [2, 14] and bytes(tb.items[:112].numpy()) == bytes(a[0]) + bytes(a[1])
+        else:
+            tb.upload(b, tiles)
+            assert tb.meta.tolist() == [2, 16] and bytes(tb.items[:112].numpy()) == bytes(b[0]) + bytes(b[1])
+    cap[0] = True
+    with pytest.raises(RuntimeError, match="first use of this table happened during graph capture .run eager warm-up iterations first"):
+        B.JobTable("cpu", L.WgradJob, 8)
+    cap[0] = False
+    st = B.SiteTables("cpu", L.WgradJob, 8, name="S")
+    eager = st.upload("site", a, tiles)
+    twin = st.tables[("site", True)]
+    assert eager is st.tables[("site", False)] and eager is not twin and eager.meta.tolist() == twin.meta.tolist() == [2, 14]
+    cap[0] = True
+    assert st.upload("site", a, tiles) is twin and twin.replayed and not eager.replayed
+    with pytest.raises(L.CrdrHipError, match="first use"):
+        st.upload("never warmed up", a, tiles)
+    cap[0] = False
+    assert st.upload("site", a, tiles) is eager
+    with pytest.raises(L.CrdrHipError, match="S: an eager pass would rewrite a job table that a captured HIP graph replays"):
+        st.upload("site", b, tiles)
+    assert bytes(twin.items[:112].numpy()) == bytes(a[0]) + bytes(a[1]) and bytes(eager.items[:112].numpy()) == bytes(a[0]) + bytes(a[1])
+
+
+def test_bump_arena_recycles_addresses_and_retires_buffers(monkeypatch):
+    """batched.BumpArena: 256-byte granules; after a reset the same requests get the same addresses (what keeps the job tables unchanged from
+    step to step); a cycle that outgrew the buffer ends in ONE buffer that holds it; a superseded buffer is released one reset later, unless
+    it was current during a capture -- then it stays; nothing grows under capture."""
+    import weakref
+    from crdr_amd.hip import batched as B
+    from crdr_amd.hip import lib as L
+    cap = [False]
+    monkeypatch.setattr(B, "_capturing", lambda: cap[0])
+    ar = B.BumpArena("cpu", 4096, name="A: arena")
+    base = ar.tensor.data_ptr()
+    first = [ar.alloc(n) for n in (1, 256, 257, 1000)]
+    assert [p - base for p in first] == [0, 256, 512, 1024] and ar.off == 2048
+    ar.reset()
+    assert [ar.alloc(n) for n in (1, 256, 257, 1000)] == first and ar.tensor.data_ptr() == base
+    ar.reset()
+    ar.alloc(300)
+    ar.rewind()                                               # drop(): the same addresses again, nothing retired
+    assert ar.alloc(300) == base and ar.cycle == 512
+    ar.reset()
+    # growth: the old buffer lives until the reset AFTER the one that ends the cycle (its launch may still read it)
+    old = weakref.ref(ar.tensor)
+    ar.alloc(4096)
+    p = ar.alloc(512)
+    assert old() is not None and ar.tensor.numel() == 2 * (4096 + 512) and p == ar.tensor.data_ptr()
+    ar.alloc(8192)                                            # fits: 512 + 8192 <= 9216
+    mid = weakref.ref(ar.tensor)
+    ar.reset()                                                # 12800 bytes in the cycle, 9216 in the buffer: the next cycle gets one that fits
+    assert old() is not None and mid() is not None and ar.tensor.numel() == 2 * 12800
+    base = ar.tensor.data_ptr()
+    assert [ar.alloc(n) - base for n in (4096, 512, 8192)] == [0, 4096, 4608]
+    ar.reset()
+    assert old() is None and mid() is None and ar.tensor.data_ptr() == base
+    # a buffer that a capture used is pinned; growth under capture is refused
+    cap[0] = True
+    pinned = weakref.ref(ar.tensor)
+    ar.alloc(256)
+    with pytest.raises(L.CrdrHipError, match="A: arena too small during graph capture .run eager warm-up iterations first"):
+        ar.alloc(1 << 20)
+    ar.reset()
+    cap[0] = False
+    ar.alloc(1 << 20)
+    assert ar.tensor.data_ptr() != pinned().data_ptr()
+    for _ in range(3):
+        ar.reset()
+    assert pinned() is not None
+    # offset-addressed use (ColsumQueue's scratch): reserve() grows to twice the request and obeys the same rules
+    sc = B.BumpArena("cpu", 1024, name="A: scratch")
+    a0 = sc.reserve(1024)
+    assert a0 == sc.tensor.data_ptr() and sc.reserve(100) == a0
+    assert sc.reserve(1025) == sc.tensor.data_ptr() and sc.tensor.numel() == 2050

@@ -106,3 +106,68 @@ def test_filter_caches_created_after_capture_follow_the_replayed_updates():
     finally:
         ops.PREFER_WINOGRAD = False
         ops.filter_scope_invalidate()
+
+
+def test_eager_pass_after_capture_never_rewrites_the_replayed_colsum_table():
+    """The column-sum job table of a captured chain backward is frozen (hip/batched.py): the captured conv launches write their partial rows
+    to the addresses it held at capture time.  An eager pass of the same site with the same content leaves it alone and the next replay gives
+    the same gradients bit for bit; an eager pass whose jobs differ -- one bias gradient lives at another address -- raises instead of
+    changing what the graph computes."""
+    from crdr_amd.hip import lib as L
+    from crdr_amd.hip import ops
+    from crdr_amd.models.layer.elic_layers import ResidualBottleneckBlocks
+    from crdr_amd.trainer.graphs import SegmentGraphs
+    d = dev()
+    torch.manual_seed(0)
+    net = ResidualBottleneckBlocks(64, 32, num_blocks=2).to(d)
+    params = list(net.parameters())
+    for p in params:
+        p.grad = torch.zeros_like(p)
+    x = seeded_input("chain input", (2, 64, 16, 16)).to(d).contiguous(memory_format=torch.channels_last)
+    q, site = ops.colsum_queue(d), net._chain(False).site
+    defer = ops.DeferredWgrad(d, arena_bytes=64 << 20)   # (a queue of this test's own: its captured tables die with it)
+    prev, ops.WGRAD_DEFER = ops.WGRAD_DEFER, defer
+
+    def step():
+        for p in params:
+            p.grad.zero_()
+        net(x).square().sum().backward()
+        ops.flush_wgrads("frozen colsum table")
+
+    def grads():
+        torch.cuda.synchronize()
+        return [p.grad.clone() for p in params]
+    sg = SegmentGraphs(True)
+    try:
+        with sg.step_scope():
+            step()
+            step()
+            g_eager = grads()
+            assert all(float(g.abs().max()) > 0 for g in g_eager)
+            sg.run("chain backward", step)
+            g_graph = grads()
+            for a, b in zip(g_eager, g_graph):
+                assert torch.equal(a, b)
+            twin = q.tables.tables[(site, True)]
+            assert twin.replayed and not q.tables.tables[(site, False)].replayed
+            held = [t.clone() for t in (twin.items, twin.prefix, twin.meta)]
+            step()   # eager, same shapes: same jobs at the same addresses
+            sg.run("chain backward", step)
+            assert all(torch.equal(a, b) for a, b in zip(held, (twin.items, twin.prefix, twin.meta)))
+            for a, b in zip(g_graph, grads()):
+                assert torch.equal(a, b)
+            bias = net.block0.conv[0].bias
+            keep, bias.grad = bias.grad, torch.zeros_like(bias)   # its column sum now goes to another address
+            try:
+                with pytest.raises(L.CrdrHipError, match="re-capture the graphs"):
+                    step()
+            finally:
+                q.drop()
+                defer.drop()
+                bias.grad = keep
+            sg.run("chain backward", step)
+            assert all(torch.equal(a, b) for a, b in zip(held, (twin.items, twin.prefix, twin.meta)))
+            for a, b in zip(g_graph, grads()):
+                assert torch.equal(a, b)
+    finally:
+        ops.WGRAD_DEFER = prev

@@ -280,7 +280,7 @@ def _replay_conv(rp, key, algo, seed):
                         off = ptr - q.arena.data_ptr()
                         part = q.arena[off:off + rows * 2 * ld * 4].view(torch.float32).view(rows, 2, ld)
                         cs.append(part.double().sum(0)[:, :oc].clone())
-                    q.off, q.jobs, q.scratch_off = 0, [], 0
+                    q.drop()
         torch.cuda.synchronize()
         return ys, sig, cs
 

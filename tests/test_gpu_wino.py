@@ -466,7 +466,7 @@ def test_winograd_f4x4_epilogues_slices_groups_colsum():
             for ptr, rows, ld in r:
                 off = ptr - q.arena.data_ptr()
                 cs.append(q.arena[off:off + rows * 2 * ld * 4].view(torch.float32).view(rows, 2, ld).double().sum(0)[:, :co].clone())
-            q.off, q.jobs, q.scratch_off = 0, [], 0
+            q.drop()
             torch.cuda.synchronize()
             return ys, cs
         finally:
