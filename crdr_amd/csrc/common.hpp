@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <atomic>
+
 #include "crdr_hip.h"
 
 namespace crdr {
@@ -39,6 +41,28 @@ void profile_end(int kind, double flops, void* token, hipStream_t s);
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return cdiv(a, b) * b; }
+
+// Lift the dynamic-LDS limit of `n` kernels to the CU's 160 KB before their first launch.  `done` is the call site's flag for exactly these kernels
+// (one per kernel variant): once set, the launch path never calls the runtime for them again.  Two threads that race here both set the attribute,
+// which is harmless; launching without it is not.
+template <class K>
+inline void allow_full_lds(std::atomic<bool>& done, const K* kerns, int n) {
+  if (done.load(std::memory_order_acquire)) return;
+  for (int i = 0; i < n; ++i) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kerns[i]), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  done.store(true, std::memory_order_release);
+}
+template <class K>
+inline void allow_full_lds(std::atomic<bool>& done, K kern) { allow_full_lds(done, &kern, 1); }
+
+// compute units of the current device, rounded down to whole XCD rows of 8 (256 where the runtime cannot tell): the grid of the persistent kernels
+inline int cu_count() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
+    return n / 8 * 8;
+  }();
+  return ncu;
+}
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

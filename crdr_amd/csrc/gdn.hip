@@ -14,7 +14,6 @@
 // transforms use ReLU bottlenecks -- so this is a registered optional op, parity-tested and profiled on its own.
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 
 #include "common.hpp"
@@ -313,10 +312,7 @@ template <int NS, int OP>
 static void gdn_fused_launch_op(const GdnFusedArgs& a, hipStream_t s) {
   const size_t lds = ((size_t)2 * (NS / 2) * kGdnBM * 32 + 64 * (NS / 4)) * sizeof(float);
   static std::atomic<bool> done{false};
-  if (!done.load(std::memory_order_acquire)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gdn_fused_fwd_kernel<NS, OP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    done.store(true, std::memory_order_release);
-  }
+  allow_full_lds(done, gdn_fused_fwd_kernel<NS, OP>);
   hipLaunchKernelGGL((gdn_fused_fwd_kernel<NS, OP>), dim3(std::min(a.tiles, 256)), dim3(256), lds, s, a);
 }
 
@@ -557,10 +553,7 @@ template <int NS, bool INV>
 static void gdn_bwd1_launch_dir(const GdnBwd1Args& a, hipStream_t s) {
   const size_t lds = ((size_t)3 * (NS / 2) * kGdnBM * 32 + 64 * (NS / 4)) * sizeof(float);
   static std::atomic<bool> done{false};
-  if (!done.load(std::memory_order_acquire)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gdn_bwd_onepass_kernel<NS, INV>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    done.store(true, std::memory_order_release);
-  }
+  allow_full_lds(done, gdn_bwd_onepass_kernel<NS, INV>);
   hipLaunchKernelGGL((gdn_bwd_onepass_kernel<NS, INV>), dim3(std::min(a.tiles, 256)), dim3(256), lds, s, a);
 }
 
@@ -721,10 +714,7 @@ template <int NS>
 static void gdn_dgamma_launch(const GdnDgArgs& a, hipStream_t s) {
   const size_t lds = (size_t)6 * (NS / 2) * kGdnDgBP * 32 * sizeof(float);
   static std::atomic<bool> done{false};
-  if (!done.load(std::memory_order_acquire)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gdn_dgamma_kernel<NS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    done.store(true, std::memory_order_release);
-  }
+  allow_full_lds(done, gdn_dgamma_kernel<NS>);
   hipLaunchKernelGGL(gdn_dgamma_kernel<NS>, dim3(gdn_dgamma_grid(a.tiles)), dim3(256), lds, s, a);
 }
 

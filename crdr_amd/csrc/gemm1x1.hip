@@ -3,7 +3,6 @@
 // The throw-away build switches DESIGN.md 4c's cost breakdown was measured with (ring not refilled, results not stored, no epilogue,
 // L2-resident tiles) live in tools/experiments/kernel_experiment_switches.patch, not here.  CRDR_STORE_AUX=2: non-temporal stores.
 
-#include <atomic>
 
 #include "common.hpp"
 #include "igemm_args.hpp"
@@ -365,16 +364,26 @@ void stream_variant_shape(int v, int* nb, int* stages, int* nw) {
   *nw = kStreamCfgs[v].nw;
 }
 
+// Whether variant v takes the convolution, and the LDS it needs: the whole K extent of a column tile + the ring of input stages + the column-sum
+// partials + the per-column vectors.  The first rule that fails is the answer (a forced id reports it; the built-in choice skips the variant).
+StreamFit stream_fits(const crdr_conv_desc* d, int v, size_t* lds) {
+  if (d->wlayout == 1 || d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad != 0 || d->C % 32 != 0 ||
+      (d->flags & (CRDR_EPI_GATE | CRDR_EPI_PREADD | CRDR_EPI_ACCUM)) || d->OC % 4 != 0)
+    return StreamFit::kShape;
+  const StreamCfg& sc = kStreamCfgs[v];
+  const int BN = 32 * sc.nb;
+  *lds = ((size_t)cdiv(d->C, 32) * BN * 32 + (size_t)sc.stages * 32 * sc.nw * 32 + sc.nw * 2 * BN + 4 * BN) * sizeof(float);
+  if (*lds > 160 * 1024) return StreamFit::kLds;
+  return cdiv(d->OC, BN) > 32 ? StreamFit::kColumnTiles : StreamFit::kOk;
+}
+
 void stream_launch(int v, const IgemmArgs& a, const StreamArgs& sa, const IgemmGroup& grp, unsigned grid, size_t lds, hipStream_t s) {
   const StreamCfg& sc = kStreamCfgs[v];
   const int ops = ((a.flags & CRDR_EPI_RES) ? 1 : 0) | ((a.flags & (CRDR_EPI_RELUMASK | CRDR_EPI_LRELUMASK)) ? 2 : 0);
   const int b6 = (a.flags & CRDR_CONV_BF16X6) ? 1 : 0;
   auto kern = b6 ? sc.kern6[ops] : sc.kern[ops];
   static std::atomic<bool> attr_done[2][16][4];
-  if (!attr_done[b6][v][ops].load(std::memory_order_acquire)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done[b6][v][ops].store(true, std::memory_order_release);
-  }
+  allow_full_lds(attr_done[b6][v][ops], kern);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * sc.nw), lds, s, a, sa, grp);
 }
 

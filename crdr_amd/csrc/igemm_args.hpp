@@ -78,6 +78,8 @@ struct StreamArgs {
 };
 int stream_num_variants();
 void stream_variant_shape(int v, int* nb, int* stages, int* nw);
+enum class StreamFit { kOk, kShape, kLds, kColumnTiles };
+StreamFit stream_fits(const crdr_conv_desc* d, int v, size_t* lds);
 void stream_launch(int v, const IgemmArgs& a, const StreamArgs& sa, const IgemmGroup& grp, unsigned grid, size_t lds, hipStream_t s);
 
 }  // namespace crdr

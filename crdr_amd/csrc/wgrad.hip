@@ -10,8 +10,8 @@
 // into the parameter layout [I][J][T].
 
 #include <algorithm>
-#include <atomic>
 
+#include "algo_id.hpp"
 #include "common.hpp"
 #include "wgrad_args.hpp"
 
@@ -548,6 +548,79 @@ struct WPlan {
   size_t lds, ws_bytes;
 };
 
+// tile configuration + pixel split by a small cost model; the first of equally cheap plans wins
+static void choose_wtile(const crdr_wgrad_desc* d, const WgradArgs& a, int ncols, int ntapg, int G, int* bc, int* bs) {
+  double best = 1e300;
+  const bool sqq = (d->algo & CRDR_WGRAD_SQUARE_Q) != 0;
+  for (int c = 0; c < kNumWCfgs; ++c) {
+    const WCfg& t = kWCfgs[c];
+    if (sqq && !t.kern_sq) continue;
+    const int BI = 32 * t.wm * t.mb, BJ = 32 * t.wn * t.nb;
+    const long long tiles = (long long)cdiv(d->PC, BI) * cdiv(ncols, BJ) * ntapg;
+    const int waves_per_block = t.wm * t.wn;
+    for (int ns = 1; ns <= 256; ns *= 2) {
+      if (ns > 1 && a.ntiles / ns < 4) break;
+      const long long blocks = tiles * ns * G;
+      const double slots = 256.0 * std::max(1, 4 / waves_per_block);  // blocks that run at full MFMA rate at once
+      const double per_tile = 16.0 * t.mb * t.nb * 64.0 * ((d->algo & CRDR_WGRAD_BF16X3) ? 0.3 : ((d->algo & CRDR_WGRAD_BF16X6) ? 0.5 : 1.0)) + 400.0;
+      double cost = std::ceil(blocks / slots) * ((double)cdiv(a.ntiles, ns) * per_tile + 4000.0);
+      cost += (double)ns * ntapg * d->PC * ncols * 4.0 / 1500.0;  // slab write + read
+      if (cost < best) { best = cost; *bc = c; *bs = ns; }
+    }
+  }
+}
+
+// forced: a Winograd slab kernel, strips of 16 pixel columns split bs ways: F(3x3, 2x2) (wino_wgrad.hip, strips of 2 tile rows) or, f4,
+// F(3x3, 4x4) (wino4_wgrad.hip, strips of 4; a 5x5 gradient is four 3x3 sub-problems)
+static int plan_wino_slabs(const crdr_wgrad_desc* d, WPlan* pl, int G, bool f4, int bs) {
+  WgradArgs& a = pl->a;
+  const bool k3 = d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad >= 0 && d->pad <= 2;
+  const bool k5 = d->kh == 5 && d->kw == 5 && (d->stride == 1 || d->stride == 2) && d->pad == 2;
+  const bool exact = !a.smallj && !(d->algo & CRDR_WGRAD_BF16X3);
+  if (f4)
+    CRDR_REQUIRE((k3 || k5) && exact,
+                 "wgrad: the Winograd F(3x3, 4x4) kernel takes 3x3 stride-1 and 5x5 (pad 2, stride 1 or 2) weight gradients with QC > 4 (exact fp32 only)");
+  else
+    CRDR_REQUIRE(k3 && exact, "wgrad: the Winograd kernel takes 3x3 stride-1 weight gradients with QC > 4 (exact fp32 only)");
+  const int rows = f4 ? 4 : 2;
+  const long long strips = (long long)d->N * ((d->PH + rows - 1) / rows) * ((d->PW + 15) / 16);
+  CRDR_REQUIRE(strips / bs >= 1, "wgrad: forced split %d too deep for %lld strips", bs, strips);
+  pl->wino = f4 ? 2 : 1; pl->cfg = -1;
+  a.nsplit = bs; a.jtiles = cdiv(d->QC, f4 ? 32 : 64);
+  pl->grid = dim3(cdiv(d->PC, 64) * a.jtiles * (f4 && !k3 ? 4 : 1), bs, G);
+  pl->lds = 0;
+  a.slab_elems = (long long)bs * a.T * d->PC * d->QC;
+  pl->ws_bytes = (size_t)G * bs * a.T * d->PC * d->QC * sizeof(float);
+  return 0;
+}
+
+// the direct kernels: the caller's configuration and split (id.family == kAlgoTiled, or an id that names nothing), else the cost model's
+static int plan_direct(const crdr_wgrad_desc* d, WPlan* pl, int G, const AlgoId& id) {
+  WgradArgs& a = pl->a;
+  const int ncols = a.smallj ? a.T * 4 : d->QC;   // GEMM columns per launch
+  const int ntapg = a.smallj ? 1 : a.T;           // tap groups = grid.y = slabs per split
+  int bc = -1, bs = 1;
+  if (id.family == kAlgoBuiltIn) {
+    choose_wtile(d, a, ncols, ntapg, G, &bc, &bs);
+  } else {
+    bc = id.index;
+    bs = wgrad_algo_splits(id);
+    CRDR_REQUIRE(id.family == kAlgoTiled, "wgrad: forced config %d out of range", bc);
+    CRDR_REQUIRE(!(d->algo & CRDR_WGRAD_SQUARE_Q) || kWCfgs[bc].kern_sq, "wgrad: config %d has no CRDR_WGRAD_SQUARE_Q form", bc);
+    CRDR_REQUIRE(bs == 1 || a.ntiles / bs >= 1, "wgrad: forced split %d too deep for %d pixel tiles", bs, a.ntiles);
+  }
+  CRDR_REQUIRE(bc >= 0, "wgrad: no tile config");
+  const WCfg& t = kWCfgs[bc];
+  const int BI = 32 * t.wm * t.mb, BJ = 32 * t.wn * t.nb;
+  pl->wino = 0; pl->cfg = bc; a.nsplit = bs; a.jtiles = cdiv(ncols, BJ);
+  pl->grid = dim3(cdiv(d->PC, BI) * a.jtiles, ntapg, bs * G);
+  pl->lds = (size_t)2 * 32 * (BI + BJ) * sizeof(float);
+  a.slab_elems = (long long)bs * ntapg * d->PC * ncols;
+  pl->ws_bytes = (size_t)G * bs * ntapg * d->PC * ncols * sizeof(float);
+  return 0;
+}
+
+// descriptor checks and geometry, then the planner of the family the id names
 static int build_wplan(const crdr_wgrad_desc* d, WPlan* pl, int G = 1) {
   WgradArgs& a = pl->a;
   memset(&a, 0, sizeof(a));
@@ -568,80 +641,13 @@ static int build_wplan(const crdr_wgrad_desc* d, WPlan* pl, int G = 1) {
   }
   a.ntiles = cdiv(a.M, 32);
   a.smallj = (d->QC <= 4 && a.T > 1) ? 1 : 0;
-  const int ncols = a.smallj ? a.T * 4 : d->QC;   // GEMM columns per launch
-  const int ntapg = a.smallj ? 1 : a.T;           // tap groups = grid.y = slabs per split
   a.d_hw = make_fastdiv((unsigned)(d->PH * d->PW));
   a.d_w = make_fastdiv((unsigned)d->PW);
-  double best = 1e300; int bc = -1, bs = 1;
-  const bool sqq = (d->algo & CRDR_WGRAD_SQUARE_Q) != 0;
-  CRDR_REQUIRE(!sqq || !(d->algo & (CRDR_WGRAD_BF16X3 | CRDR_WGRAD_BF16X6)), "wgrad: CRDR_WGRAD_SQUARE_Q is exact fp32");
-  for (int c = 0; c < kNumWCfgs; ++c) {
-    const WCfg& t = kWCfgs[c];
-    if (sqq && !t.kern_sq) continue;
-    const int BI = 32 * t.wm * t.mb, BJ = 32 * t.wn * t.nb;
-    const long long tiles = (long long)cdiv(d->PC, BI) * cdiv(ncols, BJ) * ntapg;
-    const int waves_per_block = t.wm * t.wn;
-    for (int ns = 1; ns <= 256; ns *= 2) {
-      if (ns > 1 && a.ntiles / ns < 4) break;
-      const long long blocks = tiles * ns * G;
-      const double slots = 256.0 * std::max(1, 4 / waves_per_block);  // blocks that run at full MFMA rate at once
-      const double per_tile = 16.0 * t.mb * t.nb * 64.0 * ((d->algo & CRDR_WGRAD_BF16X3) ? 0.3 : ((d->algo & CRDR_WGRAD_BF16X6) ? 0.5 : 1.0)) + 400.0;
-      double cost = std::ceil(blocks / slots) * ((double)cdiv(a.ntiles, ns) * per_tile + 4000.0);
-      cost += (double)ns * ntapg * d->PC * ncols * 4.0 / 1500.0;  // slab write + read
-      if (cost < best) { best = cost; bc = c; bs = ns; }
-    }
-  }
-  pl->wino = 0;
-  if ((d->algo & 0xff) - 1 == kNumWCfgs + 1) {  // forced: the Winograd F(3x3, 4x4) slab kernel (wino4_wgrad.hip), strips of 4 tiles split 2^k ways
-    const bool k3 = d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad >= 0 && d->pad <= 2;
-    const bool k5s1 = d->kh == 5 && d->kw == 5 && d->stride == 1 && d->pad == 2;
-    const bool k5s2 = d->kh == 5 && d->kw == 5 && d->stride == 2 && d->pad == 2;
-    CRDR_REQUIRE((k3 || k5s1 || k5s2) && !a.smallj && !(d->algo & CRDR_WGRAD_BF16X3),
-                 "wgrad: the Winograd F(3x3, 4x4) kernel takes 3x3 stride-1 and 5x5 (pad 2, stride 1 or 2) weight gradients with QC > 4 (exact fp32 only)");
-    bs = 1 << ((d->algo >> 8) & 0xf);
-    const long long strips = (long long)d->N * ((d->PH + 3) / 4) * ((d->PW + 15) / 16);
-    CRDR_REQUIRE(strips / bs >= 1, "wgrad: forced split %d too deep for %lld strips", bs, strips);
-    pl->wino = 2; pl->cfg = -1;
-    a.nsplit = bs; a.jtiles = cdiv(d->QC, 32);
-    pl->grid = dim3(cdiv(d->PC, 64) * a.jtiles * (k3 ? 1 : 4), bs, G);
-    pl->lds = 0;
-    a.ngroup = G;
-    a.slab_elems = (long long)bs * a.T * d->PC * d->QC;
-    pl->ws_bytes = (size_t)G * bs * a.T * d->PC * d->QC * sizeof(float);
-    return 0;
-  }
-  if ((d->algo & 0xff) - 1 == kNumWCfgs) {  // forced: the Winograd F(3x3, 2x2) slab kernel (wino_wgrad.hip), strips split 2^k ways
-    CRDR_REQUIRE(d->kh == 3 && d->kw == 3 && d->stride == 1 && !a.smallj && !(d->algo & CRDR_WGRAD_BF16X3) && d->pad >= 0 && d->pad <= 2,
-                 "wgrad: the Winograd kernel takes 3x3 stride-1 weight gradients with QC > 4 (exact fp32 only)");
-    bs = 1 << ((d->algo >> 8) & 0xf);
-    const long long strips = (long long)d->N * ((d->PH + 1) / 2) * ((d->PW + 15) / 16);
-    CRDR_REQUIRE(strips / bs >= 1, "wgrad: forced split %d too deep for %lld strips", bs, strips);
-    pl->wino = 1; pl->cfg = -1;
-    a.nsplit = bs; a.jtiles = cdiv(d->QC, 64);
-    pl->grid = dim3(cdiv(d->PC, 64) * a.jtiles, bs, G);
-    pl->lds = 0;
-    a.ngroup = G;
-    a.slab_elems = (long long)bs * a.T * d->PC * d->QC;
-    pl->ws_bytes = (size_t)G * bs * a.T * d->PC * d->QC * sizeof(float);
-    return 0;
-  }
-  if ((d->algo & 0xffff) != 0) {  // caller-forced algorithm (autotuner): (config index + 1) | log2(split) << 8
-    bc = (d->algo & 0xff) - 1;
-    bs = 1 << ((d->algo >> 8) & 0xf);
-    CRDR_REQUIRE(bc >= 0 && bc < kNumWCfgs, "wgrad: forced config %d out of range", bc);
-    CRDR_REQUIRE(!sqq || kWCfgs[bc].kern_sq, "wgrad: config %d has no CRDR_WGRAD_SQUARE_Q form", bc);
-    CRDR_REQUIRE(bs == 1 || a.ntiles / bs >= 1, "wgrad: forced split %d too deep for %d pixel tiles", bs, a.ntiles);
-  }
-  CRDR_REQUIRE(bc >= 0, "wgrad: no tile config");
-  const WCfg& t = kWCfgs[bc];
-  const int BI = 32 * t.wm * t.mb, BJ = 32 * t.wn * t.nb;
-  pl->cfg = bc; a.nsplit = bs; a.jtiles = cdiv(ncols, BJ);
-  pl->grid = dim3(cdiv(d->PC, BI) * a.jtiles, ntapg, bs * G);
-  pl->lds = (size_t)2 * 32 * (BI + BJ) * sizeof(float);
   a.ngroup = G;
-  a.slab_elems = (long long)bs * ntapg * d->PC * ncols;
-  pl->ws_bytes = (size_t)G * bs * ntapg * d->PC * ncols * sizeof(float);
-  return 0;
+  CRDR_REQUIRE(!(d->algo & CRDR_WGRAD_SQUARE_Q) || !(d->algo & (CRDR_WGRAD_BF16X3 | CRDR_WGRAD_BF16X6)), "wgrad: CRDR_WGRAD_SQUARE_Q is exact fp32");
+  const AlgoId id = wgrad_algo_decode(d->algo, kNumWCfgs);
+  if (id.family == kAlgoWino2 || id.family == kAlgoWino4) return plan_wino_slabs(d, pl, G, id.family == kAlgoWino4, wgrad_algo_splits(id));
+  return plan_direct(d, pl, G, id);
 }
 
 }  // namespace crdr
@@ -652,11 +658,7 @@ extern "C" int crdr_conv2d_wgrad_num_configs(void) { return kNumWCfgs + 1; }   /
 // Winograd slab kernels: ids crdr_conv2d_wgrad_num_configs() (F(3x3, 2x2)) .. + crdr_conv2d_wgrad_num_wino_configs() - 1 (F(3x3, 4x4))
 extern "C" int crdr_conv2d_wgrad_num_wino_configs(void) { return 2; }
 
-extern "C" size_t crdr_conv2d_wgrad_workspace(const crdr_wgrad_desc* d) {
-  WPlan pl;
-  if (build_wplan(d, &pl)) return 0;
-  return pl.ws_bytes;
-}
+extern "C" size_t crdr_conv2d_wgrad_workspace(const crdr_wgrad_desc* d) { return crdr_conv2d_wgrad_grouped_workspace(d, 1); }
 
 static int launch_wgrad_slabs(const crdr_wgrad_desc* d, const float* const* ps, const float* const* qs, int G, void* ws,
                               size_t ws_bytes, WPlan& pl, crdr_stream_t s) {
@@ -671,13 +673,9 @@ static int launch_wgrad_slabs(const crdr_wgrad_desc* d, const float* const* ps, 
     grp.p[g] = ps[g]; grp.q[g] = qs[g];
   }
   a.p = ps[0]; a.q = qs[0]; a.ws = (float*)ws;
-  if (pl.wino == 2) {
-    wino4_wgrad_launch(a, grp, pl.grid, as_stream(s));
-    CRDR_CHECK_LAUNCH("wino4_wgrad_kernel");
-    return 0;
-  } else if (pl.wino) {
-    wino_wgrad_launch(a, grp, pl.grid, as_stream(s));
-    CRDR_CHECK_LAUNCH("wino_wgrad_kernel");
+  if (pl.wino) {
+    (pl.wino == 2 ? wino4_wgrad_launch : wino_wgrad_launch)(a, grp, pl.grid, as_stream(s));
+    CRDR_CHECK_LAUNCH(pl.wino == 2 ? "wino4_wgrad_kernel" : "wino_wgrad_kernel");
     return 0;
   }
   const WCfg& t = kWCfgs[pl.cfg];
@@ -687,13 +685,20 @@ static int launch_wgrad_slabs(const crdr_wgrad_desc* d, const float* const* ps, 
   CRDR_REQUIRE(!sq || pl.wino == 0, "wgrad: CRDR_WGRAD_SQUARE_Q with a Winograd id");
   auto kern = sq ? t.kern_sq : (bf3 == 1 ? t.kern_bf3 : (bf3 == 2 ? t.kern_bf6 : t.kern));
   static std::atomic<bool> attr_done[4][64];
-  if (!attr_done[sq ? 3 : bf3][pl.cfg].load(std::memory_order_acquire)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done[sq ? 3 : bf3][pl.cfg].store(true, std::memory_order_release);
-  }
+  allow_full_lds(attr_done[sq ? 3 : bf3][pl.cfg], kern);
   hipLaunchKernelGGL(kern, pl.grid, dim3(64 * t.wm * t.wn), pl.lds, as_stream(s), a, grp);
   CRDR_CHECK_LAUNCH("wgrad_kernel");
   return 0;
+}
+
+// kind of a launch in the profile: 1 the direct kernels, 4 the F(3x3, 2x2) slab kernel, 7 / 8 the F(3x3, 4x4) one on a 3x3 / 5x5 gradient
+static int profile_kind(const WPlan& pl, const crdr_wgrad_desc* d) { return pl.wino == 2 ? (d->kh == 5 ? 8 : 7) : pl.wino ? 4 : 1; }
+
+// the deferred reduce of one problem's slabs (crdr_wgrad_reduce_batched)
+static void fill_job(crdr_wgrad_job* job, const crdr_wgrad_desc* d, const WgradArgs& a, const float* slab, float* g) {
+  job->slab = slab; job->g = g;
+  job->PC = d->PC; job->QC = d->QC; job->gI = d->gI; job->gJ = d->gJ; job->T = a.T; job->nsplit = a.nsplit;
+  job->smallj = a.smallj; job->accumulate = d->accumulate; job->gJtot = 0; job->reserved = 0;
 }
 
 extern "C" int crdr_conv2d_wgrad(const crdr_wgrad_desc* d, const float* p, const float* q, float* g, void* ws,
@@ -708,21 +713,7 @@ extern "C" int crdr_conv2d_wgrad(const crdr_wgrad_desc* d, const float* p, const
   hipLaunchKernelGGL(wgrad_reduce, dim3(blocks), dim3(256), 0, as_stream(s), (const float*)ws, g, d->PC, d->QC, d->gI,
                      d->gJ, a.T, a.nsplit, d->accumulate, a.smallj);
   CRDR_CHECK_LAUNCH("wgrad_reduce");
-  profile_end(pl.wino == 2 ? (d->kh == 5 ? 8 : 7) : pl.wino ? 4 : 1, 2.0 * (double)a.M * d->gI * d->gJ * a.T, prof, as_stream(s));
-  return 0;
-}
-
-extern "C" int crdr_conv2d_wgrad_partial(const crdr_wgrad_desc* d, const float* p, const float* q, float* g, void* slab,
-                                         size_t slab_bytes, crdr_wgrad_job* job, crdr_stream_t s) {
-  CRDR_REQUIRE(g && job, "wgrad_partial: null pointer");
-  WPlan pl;
-  void* prof = profile_begin(as_stream(s));
-  if (int rc = launch_wgrad_slabs(d, &p, &q, 1, slab, slab_bytes, pl, s)) return rc;
-  const WgradArgs& a = pl.a;
-  job->slab = (const float*)slab; job->g = g;
-  job->PC = d->PC; job->QC = d->QC; job->gI = d->gI; job->gJ = d->gJ; job->T = a.T; job->nsplit = a.nsplit;
-  job->smallj = a.smallj; job->accumulate = d->accumulate; job->gJtot = 0; job->reserved = 0;
-  profile_end(pl.wino == 2 ? (d->kh == 5 ? 8 : 7) : pl.wino ? 4 : 1, 2.0 * (double)a.M * d->gI * d->gJ * a.T, prof, as_stream(s));
+  profile_end(profile_kind(pl, d), 2.0 * (double)a.M * d->gI * d->gJ * a.T, prof, as_stream(s));
   return 0;
 }
 
@@ -742,14 +733,18 @@ extern "C" int crdr_conv2d_wgrad_partial_grouped(const crdr_wgrad_desc* d, const
   if (int rc = launch_wgrad_slabs(d, ps, qs, G, slab, slab_bytes, pl, s)) return rc;
   const WgradArgs& a = pl.a;
   for (int g = 0; g < G; ++g) {
-    crdr_wgrad_job* job = jobs + g;
     CRDR_REQUIRE(gs[g], "wgrad_partial_grouped: null gradient (problem %d)", g);
-    job->slab = (const float*)slab + (size_t)g * a.slab_elems; job->g = gs[g];
-    job->PC = d->PC; job->QC = d->QC; job->gI = d->gI; job->gJ = d->gJ; job->T = a.T; job->nsplit = a.nsplit;
-    job->smallj = a.smallj; job->accumulate = d->accumulate; job->gJtot = 0; job->reserved = 0;
+    fill_job(jobs + g, d, a, (const float*)slab + (size_t)g * a.slab_elems, gs[g]);
   }
-  profile_end(pl.wino == 2 ? (d->kh == 5 ? 8 : 7) : pl.wino ? 4 : 1, 2.0 * (double)G * a.M * d->gI * d->gJ * a.T, prof, as_stream(s));
+  profile_end(profile_kind(pl, d), 2.0 * (double)G * a.M * d->gI * d->gJ * a.T, prof, as_stream(s));
   return 0;
+}
+
+// the grouped entry point at G = 1
+extern "C" int crdr_conv2d_wgrad_partial(const crdr_wgrad_desc* d, const float* p, const float* q, float* g, void* slab,
+                                         size_t slab_bytes, crdr_wgrad_job* job, crdr_stream_t s) {
+  CRDR_REQUIRE(g && job, "wgrad_partial: null pointer");
+  return crdr_conv2d_wgrad_partial_grouped(d, &p, &q, &g, 1, slab, slab_bytes, job, s);
 }
 
 extern "C" int crdr_wgrad_reduce_batched(const crdr_wgrad_job* jobs, const int64_t* prefix, const int64_t* meta,

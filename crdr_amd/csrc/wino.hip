@@ -30,7 +30,6 @@
 //   the element-wise epilogue of the implicit-GEMM kernel (same order of operations) with dword buffer accesses whose per-element
 //   offset is a scalar: 32 lanes = 32 consecutive channels of one pixel.
 #include <algorithm>
-#include <atomic>
 
 #include "common.hpp"
 #include "igemm_args.hpp"
@@ -589,17 +588,10 @@ int wino_launch(const crdr_conv_desc* d, int variant, IgemmArgs a, const IgemmTa
   CRDR_REQUIRE(wino_eligible(d, G), "conv2d: the Winograd kernel takes 3x3 / 5x5 stride-1 convolutions (C %% 4 == 0, no gate / pre-add epilogue)");
   const int ks = wino_ks(d), kk = d->kh, nt = kk * kk;
   WinoTaps wt;
-  int dmin = 127;
-  for (int t = 0; t < nt; ++t) dmin = std::min(dmin, (int)(signed char)(taps.packed[t] & 0xff));
+  int dmin, win[25];
+  if (int rc = tap_window(taps, kk, "Winograd", true, win, &dmin)) return rc;
   for (int t = 0; t < 36; ++t) wt.widx[t] = -1;
-  for (int t = 0; t < nt; ++t) {
-    const int v = taps.packed[t];
-    const int dh = (int)(signed char)(v & 0xff) - dmin, dw = (int)(signed char)((v >> 8) & 0xff) - dmin;
-    CRDR_REQUIRE(dh >= 0 && dh < kk && dw >= 0 && dw < kk, "conv2d: Winograd: tap offsets are not a %dx%d window", kk, kk);
-    wt.widx[dh * (3 * ks) + dw] = v >> 16;
-  }
-  for (int a2 = 0; a2 < kk; ++a2)
-    for (int b2 = 0; b2 < kk; ++b2) CRDR_REQUIRE(wt.widx[a2 * (3 * ks) + b2] >= 0, "conv2d: Winograd: incomplete %dx%d window", kk, kk);
+  for (int t = 0; t < nt; ++t) wt.widx[(t / kk) * (3 * ks) + t % kk] = win[t];
   const int ntile = cdiv(d->OC, 64), kchunks = cdiv(d->C, 8);
   {
     const long long total = (long long)ntile * ks * ks * kchunks * 128;
@@ -619,11 +611,7 @@ int wino_launch(const crdr_conv_desc* d, int variant, IgemmArgs a, const IgemmTa
   a.GW = cdiv(d->OW, 16);
   a.si = -dmin;   // the patch starts `si` pixels above / left of its first output pixel
   a.cs_rows = wino_colsum_rows(d);
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    return n / 8 * 8;
-  }();
+  const int ncu = cu_count();
   // N tiles: full 64-channel ones, then either one padded tile for the tail (variant 0) or pair tiles (variant 1, two patches each)
   const int gx = d->N * a.GH * a.GW;
   const bool pairs = variant == 1;
@@ -631,11 +619,8 @@ int wino_launch(const crdr_conv_desc* d, int variant, IgemmArgs a, const IgemmTa
   const int gyn = pairs ? d->OC / 64 : ntile, npair = pairs ? (gx + 1) / 2 : 0;
   const int total = (gx * gyn + npair) * G;
   static std::atomic<bool> attr_done[2];
-  if (!attr_done[variant].load(std::memory_order_acquire)) {
-    (void)hipFuncSetAttribute(pairs ? reinterpret_cast<const void*>(wino_kernel<true>) : reinterpret_cast<const void*>(wino_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done[variant].store(true, std::memory_order_release);
-  }
+  if (pairs) allow_full_lds(attr_done[1], wino_kernel<true>);
+  else allow_full_lds(attr_done[0], wino_kernel<false>);
   if (pairs) {
     const size_t lds = (size_t)(WinoLds<true>::kTileFloats + 4 * 64 + 8 * 2 * 32) * sizeof(float);
     hipLaunchKernelGGL(wino_kernel<true>, dim3(std::min(total, ncu)), dim3(kNT), lds, s, a, grp, gx, gyn, npair, G);

@@ -1,9 +1,28 @@
 // Winograd F(2x2, 3x3) path of crdr_conv2d (wino.hip), planned and launched from igemm.hip.
 #pragma once
+#include <algorithm>
+
 #include "common.hpp"
 #include "igemm_args.hpp"
 
 namespace crdr {
+
+// The tap table of a k x k stride-1 convolution (plain or transposed) as a window: win[dh * k + dw] = weight-pack index of the tap `dh` rows and
+// `dw` columns from the window's first tap (-1: no such tap), *dmin = the first tap's offset from the output pixel.  `who` names the kernel in
+// the refusals.
+inline int tap_window(const IgemmTaps& taps, int k, const char* who, bool complete, int* win, int* dmin) {
+  *dmin = 127;
+  for (int t = 0; t < k * k; ++t) *dmin = std::min(*dmin, (int)(signed char)(taps.packed[t] & 0xff));
+  for (int t = 0; t < k * k; ++t) win[t] = -1;
+  for (int t = 0; t < k * k; ++t) {
+    const int v = taps.packed[t];
+    const int dh = (int)(signed char)(v & 0xff) - *dmin, dw = (int)(signed char)((v >> 8) & 0xff) - *dmin;
+    CRDR_REQUIRE(dh >= 0 && dh < k && dw >= 0 && dw < k, "conv2d: %s: tap offsets are not a %dx%d window", who, k, k);
+    win[dh * k + dw] = v >> 16;
+  }
+  for (int t = 0; complete && t < k * k; ++t) CRDR_REQUIRE(win[t] >= 0, "conv2d: %s: incomplete %dx%d window", who, k, k);
+  return 0;
+}
 
 bool wino_eligible(const crdr_conv_desc* d, int G);
 size_t wino_workspace(const crdr_conv_desc* d, int G);   // bytes of transformed filters

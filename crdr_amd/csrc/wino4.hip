@@ -28,7 +28,6 @@
 //   Every lane transforms the 6 x 6 patch of its tile for its channel in registers (12 fma-class operations per 1-D transform) and
 //   the wave issues 72 MFMAs; the work is laid out by hand in 72 slots of one MFMA + its share of loads / transform / DMA.
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 
 #include "common.hpp"
@@ -971,26 +970,16 @@ static int wino4_taps(const crdr_conv_desc* d, const IgemmTaps& taps, Wino4Taps&
     for (int t = 0; t < 9; ++t) wt.widx[v][t] = -1;
   si = 1;
   if (mode == 1) {
-    int dmin = 127;
-    for (int t = 0; t < 9; ++t) dmin = std::min(dmin, (int)(signed char)(taps.packed[t] & 0xff));
-    for (int t = 0; t < 9; ++t) {
-      const int v = taps.packed[t];
-      const int dh = (int)(signed char)(v & 0xff) - dmin, dw = (int)(signed char)((v >> 8) & 0xff) - dmin;
-      CRDR_REQUIRE(dh >= 0 && dh < 3 && dw >= 0 && dw < 3, "conv2d: Winograd F(4x4): tap offsets are not a 3x3 window");
-      wt.widx[0][dh * 3 + dw] = v >> 16;
-    }
-    for (int t = 0; t < 9; ++t) CRDR_REQUIRE(wt.widx[0][t] >= 0, "conv2d: Winograd F(4x4): incomplete 3x3 window");
+    int dmin;
+    if (int rc = tap_window(taps, 3, "Winograd F(4x4)", true, wt.widx[0], &dmin)) return rc;
     si = -dmin;   // the patch starts `si` pixels above / left of its first output pixel
   } else if (mode == 4) {
     // taps (dh, dw) relative to the window's first: sub-filter (bi, bj) element (a, b) = tap (3 bi + a, 3 bj + b), absent past the 5th
-    int dmin = 127;
-    for (int t = 0; t < 25; ++t) dmin = std::min(dmin, (int)(signed char)(taps.packed[t] & 0xff));
-    for (int t = 0; t < 25; ++t) {
-      const int v = taps.packed[t];
-      const int dh = (int)(signed char)(v & 0xff) - dmin, dw = (int)(signed char)((v >> 8) & 0xff) - dmin;
-      CRDR_REQUIRE(dh >= 0 && dh < 5 && dw >= 0 && dw < 5, "conv2d: Winograd F(4x4): tap offsets are not a 5x5 window");
-      wt.widx[(dh / 3) * 2 + dw / 3][(dh % 3) * 3 + dw % 3] = v >> 16;
-    }
+    int dmin, win[25];
+    if (int rc = tap_window(taps, 5, "Winograd F(4x4)", false, win, &dmin)) return rc;
+    for (int dh = 0; dh < 5; ++dh)
+      for (int dw = 0; dw < 5; ++dw)
+        if (win[dh * 5 + dw] >= 0) wt.widx[(dh / 3) * 2 + dw / 3][(dh % 3) * 3 + dw % 3] = win[dh * 5 + dw];
     si = -dmin;
   } else if (mode == 2) {
     // out[o] = sum_t w[t] x[2 o - 2 + t], t = 2 a + p: sub-filter (ph, pw) element (a, b) = w[2 a + ph][2 b + pw] over the parity plane
@@ -1065,11 +1054,7 @@ int wino4_launch(const crdr_conv_desc* d, IgemmArgs a, const IgemmTaps& taps, co
   a.GW = geo == 2 ? 1 : cdiv(gw, wino4_tile_cols(geo));
   a.si = si;
   a.cs_rows = wino4_colsum_rows(d);
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-    return n / 8 * 8;
-  }();
+  const int ncu = cu_count();
   const int gx = wino4_patches(d, mode);
   const int total = gx * ntile * G * a.so * a.so;
   using Kern = void (*)(const IgemmArgs, const IgemmGroup, int, int, int);
@@ -1078,15 +1063,8 @@ int wino4_launch(const crdr_conv_desc* d, IgemmArgs a, const IgemmTaps& taps, co
   static const Kern kerns[4][2][2][3] = {W4_CLS(0), W4_CLS(1), W4_CLS(2), W4_CLS(3)};   // [epilogue class][split][form][geometry]
 #undef W4_CLS
 #undef W4_ROW
-  static std::atomic<bool> attr_done;
-  if (!attr_done.load(std::memory_order_acquire)) {
-    for (int ec = 0; ec < 4; ++ec)
-      for (int sp = 0; sp < 2; ++sp)
-        for (int f = 0; f < 2; ++f)
-          for (int g = 0; g < 3; ++g)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kerns[ec][sp][f][g]), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done.store(true, std::memory_order_release);
-  }
+  static std::atomic<bool> attr_done;   // (one flag for the whole table: the first launch lifts the limit of every form)
+  allow_full_lds(attr_done, &kerns[0][0][0][0], 4 * 2 * 2 * 3);
   const size_t lds = (size_t)(kLdsFloats4 + 2 * 4 * kBN4 + 4) * sizeof(float);   // (+ the split-K ticket flag)
   // tile order by a traffic estimate (each XCD has its own 4 MB L2; an XCD's ~32 concurrent workgroups walk consecutive tiles).  Patch-major: the
   // input once, but every round of resident workgroups touches every filter block of the launch again on every XCD unless they all fit L2

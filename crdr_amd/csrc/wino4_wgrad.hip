@@ -32,7 +32,6 @@
 //     (ph, pw) correlates P with the parity plane Q[2 y + ph][2 x + pw] at pad 1: the Q strip is read with pixel stride 2.
 // In both, Q row u / column c of a strip is image pixel qs (4 tr + u) + oy / qs (16 sc + c) + ox with (qs, oy, ox) per sub-problem.
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 
 #include "common.hpp"
@@ -328,10 +327,7 @@ __global__ __launch_bounds__(256) void wino4_wgrad_kernel(const WgradArgs p_, co
 
 void wino4_wgrad_launch(const WgradArgs& a, const WgradGroup& grp, dim3 grid, hipStream_t s) {
   static std::atomic<bool> attr_done{false};
-  if (!attr_done.load(std::memory_order_acquire)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wino4_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done.store(true, std::memory_order_release);
-  }
+  allow_full_lds(attr_done, wino4_wgrad_kernel);
   hipLaunchKernelGGL(wino4_wgrad_kernel, grid, dim3(256), (size_t)2 * kStage * sizeof(float), s, a, grp);
 }
 

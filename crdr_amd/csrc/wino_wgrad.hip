@@ -19,7 +19,6 @@
 // the layout of wgrad_kernel's slabs ([split][tap][PC][QC]), so the deferred fixed-order reduce (wgrad_reduce_batched) and
 // everything behind it are unchanged.  fp32 arithmetic throughout (transforms: +-1 and halves).
 #include <algorithm>
-#include <atomic>
 
 #include "common.hpp"
 #include "wgrad_args.hpp"
@@ -234,10 +233,7 @@ __global__ __launch_bounds__(512) void wino_wgrad_kernel(const WgradArgs p_, con
 
 void wino_wgrad_launch(const WgradArgs& a, const WgradGroup& grp, dim3 grid, hipStream_t s) {
   static std::atomic<bool> attr_done{false};
-  if (!attr_done.load(std::memory_order_acquire)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wino_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done.store(true, std::memory_order_release);
-  }
+  allow_full_lds(attr_done, wino_wgrad_kernel);
   hipLaunchKernelGGL(wino_wgrad_kernel, grid, dim3(512), (size_t)kLdsFloats * sizeof(float), s, a, grp);
 }
 

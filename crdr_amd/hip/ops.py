@@ -6,7 +6,9 @@ to the kernels in place through its pixel stride (`ld`).  All arithmetic happens
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
+import types
 from typing import Optional, Tuple
 
 import torch
@@ -109,21 +111,31 @@ WINO4 = os.environ.get("CRDR_WINO4", "1") != "0"         # 0: ... never the F(4x
 PREFER_WINOGRAD = False
 
 
+@functools.lru_cache(maxsize=None)
+def _ids():
+    """Where the kernel families sit among the forced-algorithm ids (layout: csrc/algo_id.hpp), read from the library once.  Library constants
+    only: what the switches WINOGRAD / WINO4 leave of them is decided where a list is asked for.  -1: the library has no such kernel.
+    (crdr_conv2d_wgrad_num_configs() counts the F(2x2) slab kernel: the F(4x4) one is the id behind it.)"""
+    lib = L.load()
+    n, ns, nw = lib.crdr_conv2d_num_configs(), lib.crdr_conv2d_num_stream_configs(), lib.crdr_conv2d_num_wino_configs()
+    return types.SimpleNamespace(stream=tuple(range(n + 1, n + 1 + ns)), wino=tuple(range(n + 1 + ns, n + 1 + ns + nw)), wino4=n + ns + 3 if nw > 2 else -1,
+                                 wgrad_wino4=lib.crdr_conv2d_wgrad_num_configs() + 1 if lib.crdr_conv2d_wgrad_num_wino_configs() >= 2 else -1)
+
+
+def tile_id(cfg: int, log2_split: int = 0) -> int:   # forced id of tile configuration `cfg` (conv or weight gradient) split 2^log2_split ways
+    return (cfg + 1) | (log2_split << 8)
+
+
 def _prefer_wino(d, G: int = 1) -> int:
     """-> the Winograd algorithm id if PREFER_WINOGRAD is set and the library accepts it for this launch, else 0."""
     if not PREFER_WINOGRAD or (d.kh, d.kw, d.stride) not in (((3, 3, 1), (5, 5, 1), (5, 5, 2)) if PREFER_WINOGRAD == 4 else ((3, 3, 1), (5, 5, 1))):
         return 0
-    lib = L.load()
-    keep, algo = d.reserved, 0
-    base = lib.crdr_conv2d_num_configs() + 1 + lib.crdr_conv2d_num_stream_configs()
-    nv = lib.crdr_conv2d_num_wino_configs() if PREFER_WINOGRAD == 4 else min(2, lib.crdr_conv2d_num_wino_configs())
-    for v in reversed(range(nv)):   # (F(4x4) / the pair-tile variant where they apply)
-        d.reserved = base + v
-        if lib.crdr_conv2d_choose_algo(C.byref(d), G) == d.reserved:
-            algo = d.reserved
-            break
-    d.reserved = keep
-    return algo
+    q = L.ConvDesc.from_buffer_copy(d)
+    for wid in reversed(_ids().wino if PREFER_WINOGRAD == 4 else _ids().wino[:2]):   # (F(4x4) / the pair-tile variant where they apply)
+        q.reserved = wid
+        if L.load().crdr_conv2d_choose_algo(C.byref(q), G) == wid:
+            return wid
+    return 0
 
 
 WINO4_SPLITS = (1, 2, 3, 5, 7, 11, 15)
@@ -132,11 +144,8 @@ WINO4_SPLITS = (1, 2, 3, 5, 7, 11, 15)
 def _wgrad_wino4_ids():
     """Forced ids of the F(3x3, 4x4) weight-gradient slab kernel (wino4_wgrad.hip: the id behind the last wgrad configuration) with its strip
     splits 1 .. 256; the library refuses them for the shapes it does not take."""
-    lib = L.load()
-    if not WINOGRAD or not WINO4 or lib.crdr_conv2d_wgrad_num_wino_configs() < 2:
-        return []
-    nw = lib.crdr_conv2d_wgrad_num_configs()
-    return [(nw + 1) | (ls << 8) for ls in range(9)]
+    w4 = _ids().wgrad_wino4
+    return [tile_id(w4 - 1, ls) for ls in range(9)] if WINOGRAD and WINO4 and w4 >= 0 else []
 
 
 # Transformed filters of the F(4x4) Winograd kernel as PERSISTENT packs (round 5).  A launch that runs that kernel on registered weight packs
@@ -313,7 +322,7 @@ def _demote_if_misaligned(d, ios, G: int, explicit: bool) -> None:
     and strides, not by pointer alignment: for an output / residual / mask view at a channel offset that is not a multiple of 4 floats the
     launch would be refused by the library (it hard-fails an id it cannot honour, which is right for an EXPLICITLY forced one).  Such a
     launch takes the built-in plan instead."""
-    if explicit or (d.reserved & 0xFF) != _wino4_id():
+    if explicit or (d.reserved & 0xFF) != _ids().wino4:
         return
     for g in range(G):
         for f_ in ("y", "res", "mask"):
@@ -326,7 +335,7 @@ def _demote_if_misaligned(d, ios, G: int, explicit: bool) -> None:
 
 def _launch_conv(lib, d, ios, G: int, ws, ws_n, device):
     """crdr_conv2d_grouped, through the persistent filter cache where the launch runs the F(4x4) kernel on registered weight packs."""
-    if (d.reserved & 0xFF) == _wino4_id() and all(_is_persistent_pack(int(ios[g].w)) for g in range(G)):
+    if (d.reserved & 0xFF) == _ids().wino4 and all(_is_persistent_pack(int(ios[g].w)) for g in range(G)):
         # (the key leaves the K-split bits of the algorithm id out on purpose: the block layout of the transformed filters does not depend
         # on the split count -- wino4_filter_bytes / wino4_filter_thread take no nsplit)
         wk = tuple(int(ios[g].w) for g in range(G))
@@ -378,7 +387,7 @@ def _conv_workspace(lib, d, G: int, device):
 def _tune_conv_launch(lib, d, ios, G: int, device) -> bool:
     _tune_w4_penalty[0] = 0.0
     w_, wn_ = _conv_workspace(lib, d, G, device)
-    nb = int(lib.crdr_conv2d_filter_cache_bytes(C.byref(d), G)) if (d.reserved & 0xFF) == _wino4_id() else 0
+    nb = int(lib.crdr_conv2d_filter_cache_bytes(C.byref(d), G)) if (d.reserved & 0xFF) == _ids().wino4 else 0
     wk = tuple(int(ios[g].w) for g in range(G))
     if not nb or not all(_is_persistent_pack(p_) for p_ in wk) or torch.cuda.is_current_stream_capturing():
         # (no transformed filters, or) the real launch will not find a cache (sub-block / temporary packs, or a launch first seen under
@@ -398,13 +407,9 @@ def _tune_conv_launch(lib, d, ios, G: int, device) -> bool:
 
 def _stream_ids():
     """Forced-algorithm ids of the streaming 1x1 variants and of the Winograd 3x3 kernel (the library rejects them for other shapes)."""
-    lib = L.load()
-    n = lib.crdr_conv2d_num_configs()
-    ns = lib.crdr_conv2d_num_stream_configs()
-    nw = lib.crdr_conv2d_num_wino_configs()
-    ids = [n + 1 + v for v in range(ns)] + ([n + 1 + ns + v for v in range(nw if WINO4 else min(nw, 2))] if WINOGRAD else [])
-    if WINOGRAD and WINO4 and nw > 2:   # the F(4x4) kernel with 2, 3, 4, 6, 8, 12 or 16 K splits per tile (bits 8..11 = splits - 1): launches with fewer tiles than CUs
-        ids += [(n + 1 + ns + 2) | (v << 8) for v in WINO4_SPLITS]
+    ids = list(_ids().stream) + (list(_ids().wino if WINO4 else _ids().wino[:2]) if WINOGRAD else [])
+    if WINOGRAD and WINO4 and _ids().wino4 >= 0:   # the F(4x4) kernel with 2, 3, 4, 6, 8, 12 or 16 K splits per tile (bits 8..11 = splits - 1): launches with fewer tiles than CUs
+        ids += [_ids().wino4 | (v << 8) for v in WINO4_SPLITS]
     return ids
 
 
@@ -418,11 +423,6 @@ TUNE_REJECTED = []   # (key, algo, measured disagreement) of every candidate ref
 TUNE_SKIPPED = []    # keys whose tuning was put off because the call's result was all zero (no scale to compare candidates against)
 TUNE_ZERO_RETRIES = 3   # ... at most this often per key; then the built-in plan is cached for it
 _tune_zero_seen = {}
-
-
-def _wino4_id() -> int:
-    lib = L.load()
-    return lib.crdr_conv2d_num_configs() + 1 + lib.crdr_conv2d_num_stream_configs() + 2 if lib.crdr_conv2d_num_wino_configs() > 2 else -1
 
 
 def _autotune(key, ncfg: int, max_log2_split: int, run, extra=(), penalty=None, result=None, reset=None, agree: float = 2e-5) -> int:
@@ -452,14 +452,14 @@ def _autotune(key, ncfg: int, max_log2_split: int, run, extra=(), penalty=None, 
         return 0
     best, best_t = 0, _time_call(lambda: run(0)) + (penalty() if penalty else 0.0)
     base_t = best_t
-    cands = [(c + 1) | (ls << 8) for c in range(ncfg) for ls in range(max_log2_split + 1)] + list(extra)
+    cands = [tile_id(c, ls) for c in range(ncfg) for ls in range(max_log2_split + 1)] + list(extra)
     for algo in cands:
         try:
             if not fresh(algo):
                 continue
             if ref is not None:
                 dis = float((result() - ref).abs().max())
-                tol = TUNE_AGREE["wino4"] if ((algo & 0xff) == _wino4_id() and key[0] in ("c", "g", "m")) else agree
+                tol = TUNE_AGREE["wino4"] if ((algo & 0xff) == _ids().wino4 and key[0] in ("c", "g", "m")) else agree
                 if not dis <= tol * ref_scale:   # (NaN fails too)
                     TUNE_REJECTED.append((key, algo, dis / (ref_scale + 1e-30)))
                     continue

@@ -103,9 +103,19 @@ typedef struct crdr_conv_desc {
   int32_t ldg;   /* pixel stride of gx, gt and sig                          */
   int32_t wlayout;  /* 0: weight pack [kh*kw][wrows][wcols] (below); 1: tap-major [wrows][wcols >= 4*kh*kw] for C <= 4
                      * (RGB inputs): a K-tile then covers 8 taps x 4 channels instead of 1 tap x 32 mostly-zero channels */
-  int32_t reserved; /* 0: built-in heuristic; else a forced algorithm = (config index + 1) | log2(split-K) << 8
-                     * (what cudnn.benchmark=True does for the reference, base_trainer.py:20: time the candidates
-                     * once per shape and keep the fastest; see crdr_amd/hip/ops.py) */
+  int32_t reserved; /* 0: built-in heuristic; else a forced algorithm id (what cudnn.benchmark=True does for the reference,
+                     * base_trainer.py:20: time the candidates once per shape and keep the fastest; see crdr_amd/hip/ops.py).
+                     * With n = crdr_conv2d_num_configs(), s = ..._num_stream_configs(), and for crdr_wgrad_desc.algo (low 16 bits)
+                     * m = crdr_conv2d_wgrad_num_configs(), which counts the F(2x2) slab kernel:
+                     *   bits 0..7 of a conv id   kernel                        bits 8..11
+                     *   1 .. n                   tiled implicit GEMM           log2(split-K)
+                     *   n + 1 .. n + s           streaming 1x1                 0
+                     *   n + s + 1, n + s + 2     Winograd F(2x2), pair tiles   0
+                     *   n + s + 3                Winograd F(4x4)               K splits - 1
+                     *   bits 0..7 of a wgrad id
+                     *   1 .. m - 1               direct                        log2(pixel split)
+                     *   m                        Winograd F(3x3, 2x2) slabs    log2(strip split)
+                     *   m + 1                    Winograd F(3x3, 4x4) slabs    log2(strip split) */
   int32_t ldpre;    /* pixel stride of pre  (CRDR_EPI_PREADD)   */
   int32_t ldmask;   /* pixel stride of mask (CRDR_EPI_RELUMASK) */
 } crdr_conv_desc;
@@ -238,7 +248,7 @@ typedef struct crdr_wgrad_desc {
   int32_t kh, kw, stride, pad;
   int32_t gI, gJ;     /* dims of g (<= PC, QC): channels beyond them are layout padding and are dropped */
   int32_t accumulate; /* 1: g += ; 0: g = */
-  int32_t algo;       /* low 16 bits 0: heuristic; else forced (config index + 1) | log2(pixel split) << 8;
+  int32_t algo;       /* low 16 bits 0: heuristic; else a forced algorithm id (layout: the table at crdr_conv_desc.reserved);
                        * bit 16 (CRDR_WGRAD_BF16X3): split-bf16 products, see CRDR_CONV_BF16X3 */
 } crdr_wgrad_desc;
 #define CRDR_WGRAD_BF16X3 (1 << 16)
