@@ -540,6 +540,38 @@ def affine(x, scale, shift):
     return _Affine.apply(x, scale, shift)
 
 
+class _PixelShuffle(torch.autograd.Function):
+    """nn.PixelShuffle(2) on NHWC memory: [N, 4C, H, W] -> [N, C, 2H, 2W] (crdr_pixel_shuffle_fwd / _bwd).  Nothing is saved: the
+    backward is the inverse permutation of the cotangent, one launch."""
+
+    @staticmethod
+    def forward(ctx, x):
+        lib = L.load()
+        x, ldx = ops.nhwc(x)
+        n, c4, h, w = x.shape
+        if c4 % 4 != 0:
+            raise L.CrdrHipError(f"pixel_shuffle: {c4} input channels are not a multiple of 4")
+        c = c4 // 4
+        y = ops.empty_nhwc(n, c, 2 * h, 2 * w, x.device)
+        L.check(lib.crdr_pixel_shuffle_fwd(x.data_ptr(), ldx, n, h, w, c, y.data_ptr(), ops.ld_for(c), ops._stream()), "pixel_shuffle_fwd")
+        ctx.in_shape = (n, c4, h, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = L.load()
+        n, c4, h, w = ctx.in_shape
+        dy, lddy = ops.nhwc(dy)
+        dx = ops.empty_nhwc(n, c4, h, w, dy.device)
+        L.check(lib.crdr_pixel_shuffle_bwd(dy.data_ptr(), lddy, n, h, w, c4 // 4, dx.data_ptr(), c4, ops._stream()), "pixel_shuffle_bwd")
+        return dx
+
+
+def pixel_shuffle(x):
+    """F.pixel_shuffle(x, 2) for NHWC tensors; 12 -> 3 channels yields the image layout (pixel stride 4, zero fourth lane)."""
+    return _PixelShuffle.apply(x)
+
+
 class _Lrp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, z):
@@ -639,7 +671,68 @@ class _GaussCond(torch.autograd.Function):
         return dy, dmu, dsg, None, None, None, None
 
 
-def gauss_cond(y, mu, sigma, noise, scale_bound=0.11, lik_bound=1e-9, want_lik=False):
+class _GaussCondPhilox(torch.autograd.Function):
+    """_GaussCond with the noise drawn in the kernel: `philox_state` is the device (seed, offset) pair of the caller's generator; the
+    forward forks its own pair off it (crdr_philox_fork, so a captured graph draws fresh noise at every replay) and the backward
+    regenerates the same samples from that pair -- nothing is stored.  -> (y_hat, bits_noisy[N], bits_quant[N], lik_noisy?, lik_quant?)"""
+
+    @staticmethod
+    def forward(ctx, y, mu, sigma, philox_state, scale_bound, lik_bound, want_lik):
+        lib = L.load()
+        y, ldy = ops.nhwc(y)
+        mu, ldmu = ops.nhwc(mu)
+        sigma, ldsg = ops.nhwc(sigma)
+        n, c, h, w = y.shape
+        dev = y.device
+        ph = torch.empty(2, dtype=torch.int64, device=dev)
+        L.check(lib.crdr_philox_fork(philox_state.data_ptr(), ph.data_ptr(), (y.numel() + 3) // 4 + 1, ops._stream()), "philox_fork")
+        yhat = ops.empty_nhwc(n, c, h, w, dev)
+        bits_n = torch.zeros(n, dtype=torch.float32, device=dev)
+        bits_q = torch.zeros(n, dtype=torch.float32, device=dev)
+        lik_n = ops.empty_nhwc(n, c, h, w, dev) if want_lik else None
+        lik_q = ops.empty_nhwc(n, c, h, w, dev) if want_lik else None
+        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldyhat=c, Ctot=c, c0=0, scale_bound=scale_bound,
+                      likelihood_bound=lik_bound)
+        io = L.GcIO(y=y.data_ptr(), mu=mu.data_ptr(), sigma=sigma.data_ptr(), philox=ph.data_ptr(), yhat=yhat.data_ptr(),
+                    lik_noisy=ops._p(lik_n), lik_quant=ops._p(lik_q), bits_noisy=bits_n.data_ptr(), bits_quant=bits_q.data_ptr())
+        gauss_cond_fwd2(d, io, dev)
+        ctx.bounds = (scale_bound, lik_bound)
+        ctx.save_for_backward(y, mu, sigma, ph)
+        ctx.mark_non_differentiable(bits_q)
+        for t in (lik_n, lik_q):
+            if t is not None:
+                ctx.mark_non_differentiable(t)
+        return yhat, bits_n, bits_q, lik_n, lik_q
+
+    @staticmethod
+    def backward(ctx, dyhat, dbits_n, _dq, _dln, _dlq):
+        y, mu, sigma, ph = ctx.saved_tensors
+        lib = L.load()
+        y, ldy = ops.nhwc(y)
+        mu, ldmu = ops.nhwc(mu)
+        sigma, ldsg = ops.nhwc(sigma)
+        n, c, h, w = y.shape
+        dev = y.device
+        if dbits_n is None:
+            dbits_n = torch.zeros(n, dtype=torch.float32, device=dev)
+        dbits_n = dbits_n.contiguous()
+        lddyh = 0
+        if dyhat is not None:
+            dyhat, lddyh = ops.nhwc(dyhat)
+        dy, dmu, dsg = (ops.empty_nhwc(n, c, h, w, dev) for _ in range(3))
+        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldgrad=c, lddyhat=lddyh, Ctot=c, c0=0,
+                      scale_bound=ctx.bounds[0], likelihood_bound=ctx.bounds[1])
+        io = L.GcIO(y=y.data_ptr(), mu=mu.data_ptr(), sigma=sigma.data_ptr(), philox=ph.data_ptr(), gbits=dbits_n.data_ptr(),
+                    dyhat=ops._p(dyhat), dy=dy.data_ptr(), dmu=dmu.data_ptr(), dsigma=dsg.data_ptr())
+        L.check(lib.crdr_gauss_cond_bwd2(C.byref(d), C.byref(io), ops._stream()), "gauss_cond_bwd2")
+        return dy, dmu, dsg, None, None, None, None
+
+
+def gauss_cond(y, mu, sigma, noise, scale_bound=0.11, lik_bound=1e-9, want_lik=False, philox_state=None):
+    """noise given: those samples; noise None and `philox_state` (device int64 [seed, offset]) given: in-kernel Philox noise; both
+    None: the quantised (eval) outputs only."""
+    if noise is None and philox_state is not None:
+        return _GaussCondPhilox.apply(y, mu, sigma, philox_state, float(scale_bound), float(lik_bound), bool(want_lik))
     return _GaussCond.apply(y, mu, sigma, noise, float(scale_bound), float(lik_bound), bool(want_lik))
 
 

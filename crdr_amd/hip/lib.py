@@ -146,6 +146,8 @@ SIGNATURES = {
     "crdr_channel_norm_bwd": (_I, [C.POINTER(ChannelNormDesc), _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _SZ, _P]),
     "crdr_reflect_pad_fwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "crdr_reflect_pad_bwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "crdr_pixel_shuffle_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "crdr_pixel_shuffle_bwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "crdr_gauss_symbols": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _F, _I, _I, _I, _P, _P, _P]),
     "crdr_philox_fork": (_I, [_P, _P, C.c_uint64, _P]),
     "crdr_philox_uniform": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),

@@ -1,6 +1,6 @@
 """Stage-1 model: ELIC transforms + Minnen20 hyperprior + Charm context model
 (src/models/comp_model/hyperprior_model.py:21-264 and hyperprior_charm_model.py:20-147, merged: the plain
-hyperprior variants without Charm are ablations outside the CRDR hot path)."""
+hyperprior variants without Charm subclass this one and put an adapter in the Charm's place, hyperprior_model.py)."""
 from __future__ import annotations
 
 import os

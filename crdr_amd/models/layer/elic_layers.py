@@ -12,10 +12,29 @@ from crdr_amd.hip import functional as HF
 from .hip_layers import HipConv2d, HipConvTranspose2d
 
 
+class SubPixelConv(nn.Module):
+    """The reference's `nn.Sequential(Conv2d(in, 4 out, k, padding=k // 2), PixelShuffle(2))` (elic_layers.py:16-20) with its key schema:
+    the conv is child "0" and there are no other keys.  The following stage's InterpChAtt scale / shift stay in the conv epilogue: conv
+    channel 4c + k becomes output channel c, so the [C] vectors enter repeated four times (torch.repeat_interleave(v, 4), written as a
+    view + reshape that never synchronises) and autograd's backward of that expand sums the groups of four."""
+
+    def __init__(self, in_ch: int, out_ch: int, kernel_size: int):
+        super().__init__()
+        self.add_module("0", HipConv2d(in_ch, 4 * out_ch, kernel_size, padding=kernel_size // 2))
+
+    def __getitem__(self, i):
+        return getattr(self, str(i))
+
+    def forward(self, x, affine=None):
+        if affine is not None:
+            affine = tuple(v.reshape(-1, 1).expand(-1, 4).reshape(-1) for v in affine)
+        return HF.pixel_shuffle(self[0](x, affine=affine))
+
+
 def up_conv(in_ch: int, out_ch: int, kernel_size: int, pixel_shuffle: bool):
     assert kernel_size == 5, "only kernel_size=5 (the ELIC setting) is supported"
     if pixel_shuffle:
-        raise NotImplementedError("pixel_shuffle up-sampling is not used by any CRDR config")
+        return SubPixelConv(in_ch, out_ch, kernel_size)
     return HipConvTranspose2d(in_ch, out_ch, kernel_size, stride=2, padding=2, output_padding=1)
 
 

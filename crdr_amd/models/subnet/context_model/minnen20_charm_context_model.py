@@ -64,37 +64,6 @@ class Minnen20CharmContextModel(BaseContextModel):
     def _support(self, hats: List[Tensor]) -> List[Tensor]:
         return hats if self.max_support_slices < 0 else hats[: self.max_support_slices]
 
-    # ---- noise: Philox state (seed, offset) on the device; the fused kernels draw U(-1/2, 1/2) from it and the backward
-    # regenerates the same samples (crdr_gauss_cond_fwd2).  Seeded per rank by the trainer (seed_noise).
-    def _philox(self, device) -> Tensor:
-        st = getattr(self, "_philox_state", None)
-        if st is None or st.device != device:
-            seed = getattr(self, "_noise_seed", None)
-            if seed is None:   # never seeded by a trainer: still one stream per rank
-                from crdr_amd.trainer import dist as _D
-                seed = (torch.initial_seed() + 7919 * (_D.rank() + 1)) & 0x7FFFFFFFFFFFFFFF
-            st = torch.tensor([int(seed), int(getattr(self, "_noise_offset", 0))], dtype=torch.int64, device=device)
-            self._philox_state = st
-        return st
-
-    def seed_noise(self, seed: int, offset: int = 0) -> None:
-        self._noise_seed = int(seed) & 0x7FFFFFFFFFFFFFFF
-        self._noise_offset = int(offset)
-        self._philox_state = None
-
-    def noise_state(self) -> Dict:
-        """(seed, offset) of the in-kernel noise generator, for the trainer's checkpoint: a resumed run continues the
-        sequence instead of replaying it from offset 0.  Synchronises."""
-        st = getattr(self, "_philox_state", None)
-        if st is None:
-            return {"seed": getattr(self, "_noise_seed", None), "offset": int(getattr(self, "_noise_offset", 0))}
-        seed, off = st.tolist()
-        return {"seed": int(seed), "offset": int(off)}
-
-    def load_noise_state(self, state: Dict) -> None:
-        if state and state.get("seed") is not None:
-            self.seed_noise(state["seed"], state.get("offset", 0))
-
     def _record(self, run) -> None:
         """parity tests read the rounding decisions (round(y_hat_pre - mu) per slice)"""
         if getattr(self, "record_symbols", None) is not None:
@@ -139,18 +108,6 @@ class Minnen20CharmContextModel(BaseContextModel):
         return yh, lik
 
     # ---- codec paths (GPU transforms, host rANS)
-    codec_profile = None  # shared with the model's compress / decompress (wall-time split {charm, rans})
-
-    def _tick(self, key, t0=None):
-        import time
-        if self.codec_profile is None:
-            return 0.0
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        if key is not None:
-            self.codec_profile[key] = self.codec_profile.get(key, 0.0) + (t - t0)
-        return t
-
     @torch.no_grad()
     def forward_compress_device(self, y: Tensor, hyper_out: Tensor, entropy_model_y):
         """GPU half of forward_compress (:143-187): all transforms, then ONE launch turns (y, mu, sigma) into the int32 symbols
@@ -176,20 +133,6 @@ class Minnen20CharmContextModel(BaseContextModel):
         from crdr_amd.hip import charm
         return charm.charm_forward(self, y, hyper_out, None, None, entropy_model_y.scale_bound, entropy_model_y.likelihood_bound,
                                    True, False)
-
-    def _pinned_pair(self, shape):
-        """Two pinned int32 host buffers of (at least) `shape` elements, kept per thread (decompress_many decodes several images
-        concurrently, one thread and one stream each)."""
-        import threading
-        cache = self.__dict__.setdefault("_pin_cache", {})
-        key = threading.get_ident()
-        need = 1
-        for d in shape:
-            need *= int(d)
-        pair = cache.get(key)
-        if pair is None or pair[0].numel() < need:
-            pair = cache[key] = (torch.empty(need, dtype=torch.int32, pin_memory=True), torch.empty(need, dtype=torch.int32, pin_memory=True))
-        return pair
 
     @torch.no_grad()
     def forward_decompress(self, y_str: bytes, hyper_out: Tensor, entropy_model_y) -> Tuple[Tensor, Tensor]:

@@ -103,7 +103,7 @@ class RateDistortionTrainer(BaseTrainer):
 
     def _staged(self) -> bool:
         return D.is_dist() and bool(self.opt.get("dp_buckets", True)) and hasattr(self.comp_model, "backward_cuts") \
-            and hasattr(self.comp_model, "context_model")
+            and hasattr(self.comp_model, "context_model") and getattr(self.comp_model, "staged_backward", True)
 
     def _piece_buffers(self):
         """Flat-gradient slices of each backward piece (parameters are laid out sorted by name, so a piece is one or two

@@ -583,6 +583,18 @@ int crdr_reflect_pad_bwd(const float* dy, int N, int H, int W, int C, int lddy, 
                          crdr_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------ */
+/* sub-pixel up-sampling (the ELIC decoders' `pixel_shuffle: True` form, elic_layers.py:16-20)       */
+/* ------------------------------------------------------------------------------------------------ */
+/* nn.PixelShuffle(2) on NHWC memory (elic_layers.py:16-20): x is [N][H][W] pixels of 4C channels in torch's order
+ * ch = 4c + 2i + j, y is [N][2H][2W] pixels of C channels, y[n][2h+i][2w+j][c] = x[n][h][w][4c+2i+j].
+ * C % 4 == 0, or C == 3: then y is the image layout (pixel stride >= 4, fourth lane written as zero).  Strides are in floats, multiples
+ * of 4 and at least the row width (channel slices of wider NHWC tensors); pointers 16-byte aligned; anything else is refused.  Pure data
+ * movement: bit exact. */
+int crdr_pixel_shuffle_fwd(const float* x, int ldx, int N, int H, int W, int C, float* y, int ldy, crdr_stream_t s);
+/* its autograd, the exact inverse: dx[n][h][w][4c+2i+j] = dy[n][2h+i][2w+j][c]  (C == 3: the fourth lane of dy is ignored) */
+int crdr_pixel_shuffle_bwd(const float* dy, int lddy, int N, int H, int W, int C, float* dx, int lddx, crdr_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------ */
 /* losses                                                                                            */
 /* ------------------------------------------------------------------------------------------------ */
 /* out[0] (+)= sum (a-b)^2 ; backward da = 2 (a-b) g, db = -da   (distortion_loss.py:41-46)         */
