@@ -580,7 +580,7 @@ class _Lrp(torch.autograd.Function):
         z, ldz = ops.nhwc(z)
         n, c, h, w = a.shape
         y = ops.empty_nhwc(n, c, h, w, a.device)
-        L.check(lib.crdr_lrp(a.data_ptr(), lda, z.data_ptr(), ldz, y.data_ptr(), c, n * h * w, c, ops._stream()), "lrp")
+        L.check(lib.crdr_lrp(a.data_ptr(), lda, z.data_ptr(), ldz, y.data_ptr(), ops.ld_for(c), n * h * w, c, ops._stream()), "lrp")
         ctx.save_for_backward(z)
         return y
 
@@ -592,7 +592,8 @@ class _Lrp(torch.autograd.Function):
         z, ldz = ops.nhwc(z)
         n, c, h, w = z.shape
         dz = ops.empty_nhwc(n, c, h, w, z.device)
-        L.check(lib.crdr_lrp_bwd(dy.data_ptr(), lddy, z.data_ptr(), ldz, dz.data_ptr(), c, n * h * w, c, ops._stream()), "lrp_bwd")
+        L.check(lib.crdr_lrp_bwd(dy.data_ptr(), lddy, z.data_ptr(), ldz, dz.data_ptr(), ops.ld_for(c), n * h * w, c, ops._stream()),
+                "lrp_bwd")
         return dy, dz
 
 
@@ -793,61 +794,73 @@ def entropy_bottleneck(z, params, medians, noise, lik_bound=1e-9):
 # ---------------------------------------------------------------------------------------------------------
 # losses
 # ---------------------------------------------------------------------------------------------------------
-def _flat(t: torch.Tensor) -> torch.Tensor:
-    """The memory behind a (possibly channel-padded NHWC) tensor as a flat contiguous buffer.  Padding lanes
-    must hold equal values in both operands of a difference (they are zero by construction)."""
-    ops._require_gpu(t)
-    if t.is_contiguous():
-        return t.reshape(-1)
-    if t.dim() == 4:
-        t2, ld = ops.nhwc(t)
-        n, c, h, w = t2.shape
-        return torch.as_strided(t2, (n * h * w * ld,), (1,), t2.storage_offset())
-    return t.contiguous().reshape(-1)
+def _loss_nhwc(t: torch.Tensor) -> torch.Tensor:
+    """A [N,C,H,W] loss operand in the library's own layout: NHWC memory whose pixel stride is ld_for(C), padding lanes zero.  A tensor
+    that already has that pixel stride is taken as it is -- its padding lanes are the library's (ops.nhwc / ops.empty_nhwc make them
+    zero); anything else (NCHW memory, a channel slice of a wider buffer at any offset, a view that does not own its last padding
+    lanes) is copied, so that no foreign channel enters the sum."""
+    t2, ld = ops.nhwc(t)
+    n, c, h, w = t2.shape
+    if ld == ops.ld_for(c) and t2.storage_offset() + n * h * w * ld <= t2.untyped_storage().nbytes() // t2.element_size():
+        return t2
+    buf = ops.empty_nhwc(n, c, h, w, t2.device, zero=True)
+    buf.copy_(t2)
+    return buf
 
 
 def _same_layout(a, b):
-    fa, fb = _flat(a), _flat(b)
-    if fa.numel() != fb.numel():
-        a = a.contiguous(memory_format=torch.channels_last)
-        b = b.contiguous(memory_format=torch.channels_last)
-        fa, fb = _flat(a), _flat(b)
-    return fa, fb
+    """-> (flat a, flat b, geometry): the two operands of a difference as flat contiguous buffers in ONE element order.  Two contiguous
+    tensors (1-D, [n,1,1,1], NCHW, ...) of one element count are flattened as they are (geometry None); otherwise both must have one
+    shape, and two [N,C,H,W] tensors are both brought to padded NHWC order (_loss_nhwc; geometry (n, c, h, w, ld)), whatever memory
+    each one came in.  The decision is made on the layouts, never on the element counts alone."""
+    ops._require_gpu(a)
+    ops._require_gpu(b)
+    if a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel():
+        return a.reshape(-1), b.reshape(-1), None
+    if a.shape != b.shape:
+        raise L.CrdrHipError(f"loss operands of different shapes {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.dim() != 4:
+        return a.contiguous().reshape(-1), b.contiguous().reshape(-1), None
+    a2, b2 = _loss_nhwc(a), _loss_nhwc(b)
+    n, c, h, w = a2.shape
+    ld = ops.ld_for(c)
+    return (torch.as_strided(a2, (n * h * w * ld,), (1,), a2.storage_offset()),
+            torch.as_strided(b2, (n * h * w * ld,), (1,), b2.storage_offset()), (n, c, h, w, ld))
+
+
+def _unflat(flat, shape, geom):
+    """A gradient computed on a flat buffer of _same_layout, as a tensor of the operand's shape (NHWC memory when `geom` is set: autograd
+    takes a gradient in any strides)."""
+    if flat is None:
+        return None
+    if geom is None:
+        return flat.view(shape)
+    n, c, h, w, ld = geom
+    return flat.view(n, h, w, ld).permute(0, 3, 1, 2)[:, :c]
 
 
 class _SqDiffSum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
         lib = L.load()
-        fa, fb = _same_layout(a, b)
+        fa, fb, ctx.geom = _same_layout(a, b)
         out = torch.empty(1, dtype=torch.float32, device=a.device)
         nb = lib.crdr_reduce_workspace(fa.numel())
         ws, wsn = ops.workspace(nb, a.device)
         L.check(lib.crdr_sqdiff_sum(fa.data_ptr(), fb.data_ptr(), fa.numel(), out.data_ptr(), ws, wsn, ops._stream()), "sqdiff_sum")
-        ctx.save_for_backward(a, b)
+        ctx.shapes = (a.shape, b.shape)
+        ctx.save_for_backward(fa, fb)   # (views of a, b wherever those already had the common layout)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        a, b = ctx.saved_tensors
+        fa, fb = ctx.saved_tensors
         lib = L.load()
-        fa, fb = _same_layout(a, b)
         da = torch.empty_like(fa) if ctx.needs_input_grad[0] else None
         db = torch.empty_like(fb) if ctx.needs_input_grad[1] else None
         L.check(lib.crdr_sqdiff_bwd(fa.data_ptr(), fb.data_ptr(), fa.numel(), g.contiguous().data_ptr(), 1.0, ops._p(da),
                                     ops._p(db), ops._stream()), "sqdiff_bwd")
-        return _unflat(da, a), _unflat(db, b)
-
-
-def _unflat(flat, like):
-    """A gradient computed on `_flat(like)`'s buffer, viewed with `like`'s shape (and NHWC pixel stride)."""
-    if flat is None:
-        return None
-    like2, ld = ops.nhwc(like) if like.dim() == 4 and not like.is_contiguous() else (like, None)
-    if ld is None:
-        return flat.view(like.shape)
-    n, c, h, w = like2.shape
-    return flat.view(n, h, w, ld).permute(0, 3, 1, 2)[:, :c]
+        return _unflat(da, ctx.shapes[0], ctx.geom), _unflat(db, ctx.shapes[1], ctx.geom)
 
 
 def sqdiff_sum(a, b):
@@ -860,23 +873,23 @@ class _L1Sum(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
         lib = L.load()
-        fa, fb = _same_layout(a, b)
+        fa, fb, ctx.geom = _same_layout(a, b)
         out = torch.empty(1, dtype=torch.float32, device=a.device)
         ws, wsn = ops.workspace(lib.crdr_reduce_workspace(fa.numel()), a.device)
         L.check(lib.crdr_l1_sum(fa.data_ptr(), fb.data_ptr(), fa.numel(), out.data_ptr(), ws, wsn, ops._stream()), "l1_sum")
-        ctx.save_for_backward(a, b)
+        ctx.shapes = (a.shape, b.shape)
+        ctx.save_for_backward(fa, fb)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        a, b = ctx.saved_tensors
+        fa, fb = ctx.saved_tensors
         lib = L.load()
-        fa, fb = _same_layout(a, b)
         da = torch.empty_like(fa) if ctx.needs_input_grad[0] else None
         db = torch.empty_like(fb) if ctx.needs_input_grad[1] else None
         L.check(lib.crdr_l1_bwd(fa.data_ptr(), fb.data_ptr(), fa.numel(), g.contiguous().data_ptr(), 1.0, ops._p(da), ops._p(db),
                                 ops._stream()), "l1_bwd")
-        return _unflat(da, a), _unflat(db, b)
+        return _unflat(da, ctx.shapes[0], ctx.geom), _unflat(db, ctx.shapes[1], ctx.geom)
 
 
 def l1_sum(a, b):
@@ -924,7 +937,7 @@ class _MaxPool3s2(torch.autograd.Function):
         if ld != c:
             x = x.contiguous(memory_format=torch.channels_last)
         oh, ow = (h - 3) // 2 + 1, (w - 3) // 2 + 1
-        y = ops.empty_nhwc(n, c, oh, ow, x.device)
+        y = ops.empty_nhwc(n, c, oh, ow, x.device, ld=c)   # the kernel takes no stride: dense rows in, dense rows out
         L.check(lib.crdr_maxpool3s2_fwd(x.data_ptr(), y.data_ptr(), n, h, w, c, ops._stream()), "maxpool_fwd")
         ctx.save_for_backward(x)
         return y
@@ -937,7 +950,7 @@ class _MaxPool3s2(torch.autograd.Function):
         dy, ld = ops.nhwc(dy)
         if ld != c:
             dy = dy.contiguous(memory_format=torch.channels_last)
-        dx = ops.empty_nhwc(n, c, h, w, x.device)
+        dx = ops.empty_nhwc(n, c, h, w, x.device, ld=c)
         L.check(lib.crdr_maxpool3s2_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), n, h, w, c, ops._stream()), "maxpool_bwd")
         return dx
 
@@ -971,7 +984,7 @@ class _LpipsLayer(torch.autograd.Function):
         f0, f1, lin = ctx.saved_tensors
         lib = L.load()
         n, c, h, w = f0.shape
-        df1 = ops.empty_nhwc(n, c, h, w, f0.device)
+        df1 = ops.empty_nhwc(n, c, h, w, f0.device, ld=c)   # dense, like the f0 / f1 the forward saved
         L.check(lib.crdr_lpips_layer_bwd(f0.data_ptr(), f1.data_ptr(), lin.data_ptr(), n, h * w, c, g.contiguous().data_ptr(),
                                          df1.data_ptr(), ops._stream()), "lpips_layer_bwd")
         return None, df1, None
