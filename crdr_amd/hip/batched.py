@@ -1,6 +1,6 @@
 """Host side of the batched launches: the device job table they read and the bump arena their jobs point into.
 
-crdr_pack_weights_batched (functional.PackTable), crdr_w4_filters_batched (ops.FilterTable), crdr_wgrad_reduce_batched (ops.DeferredWgrad)
+crdr_pack_weights_batched (packs.PackTable), crdr_w4_filters_batched (packs.FilterTable), crdr_wgrad_reduce_batched (ops.DeferredWgrad)
 and crdr_colsum_finish_batched (ops.ColsumQueue) take the same device operands: an item table, a prefix sum of tiles per item and a small
 `meta` vector.  These keep their addresses and are rewritten only when their content changes, so a launch captured in a HIP graph replays
 with no host work.  What a capture freezes is decided here and nowhere else.
@@ -32,6 +32,28 @@ from . import lib as L
 
 def _capturing() -> bool:   # (never before the runtime is up: the classes work on host tensors too)
     return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+
+
+def _stream() -> int:
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _require_gpu(t: torch.Tensor):
+    if not t.is_cuda:
+        raise L.CrdrHipError("crdr_amd ops run on the HIP device only (got a CPU tensor); there is no CPU fallback")
+    if t.dtype != torch.float32:
+        raise L.CrdrHipError(f"crdr_amd ops are fp32 (got {t.dtype})")
+
+
+# Host-side bookkeeping that a captured HIP graph skips on replay (trainer/graphs.py): code that runs under capture and keeps host state in
+# step with what its launches do on the device -- packs.PackTable.refill bumps pack versions and stamps the filter caches its batched
+# launch rebuilds -- registers a callable here; SegmentGraphs.run collects them per captured segment and calls them after every replay.
+REPLAY_HOOKS = None
+
+
+def on_replay(fn) -> None:
+    if REPLAY_HOOKS is not None and fn not in REPLAY_HOOKS:
+        REPLAY_HOOKS.append(fn)
 
 
 def prefix_sums(tiles, rows: int = 1, width: int = 0):

@@ -43,6 +43,7 @@ import torch
 from . import functional as HF
 from . import lib as L
 from . import ops
+from . import packs
 from .ops import V
 
 
@@ -135,7 +136,7 @@ class CharmPlan:
             addr[name] = buf.data_ptr()
             for k in range(n):
                 kind, i = self.order[lo + k]
-                ents.append(HF.sub_pack(self.conv(kind, i, 0).weight, 0, hm, buf, k * C1 * hm, C1, hm, False, dld=hm, tstride=n * C1 * hm))
+                ents.append(packs.sub_pack(self.conv(kind, i, 0).weight, 0, hm, buf, k * C1 * hm, C1, hm, False, dld=hm, tstride=n * C1 * hm))
         # support parts: decoded slice k -> every later transform, N-concatenated in slot order: [t1][n * C1][sc]
         for k in range(ms):
             for half in ("mu", "sc"):
@@ -147,26 +148,26 @@ class CharmPlan:
                 keep.append(buf)
                 addr[("sup_" + half, k)] = buf.data_ptr()
                 for idx, (kind, j) in enumerate(cons):
-                    ents.append(HF.sub_pack(self.conv(kind, j, 0).weight, hm + k * sc, hm + (k + 1) * sc, buf, idx * C1 * sc, C1, sc, False,
+                    ents.append(packs.sub_pack(self.conv(kind, j, 0).weight, hm + k * sc, hm + (k + 1) * sc, buf, idx * C1 * sc, C1, sc, False,
                                             dld=sc, tstride=n * C1 * sc))
         for kind in ("mean", "scale", "lrp"):
             for i in range(S):
                 w = self.conv(kind, i, 0).weight
                 if i == 0 and kind != "lrp":      # slice 0: the whole first conv directly
                     b = self._alloc(t1, C1, hm)
-                    ents.append(HF.sub_pack(w, 0, hm, b, 0, C1, hm, False))
+                    ents.append(packs.sub_pack(w, 0, hm, b, 0, C1, hm, False))
                     addr[(kind, 0, "l1")] = b.data_ptr()
                     keep.append(b)
                 if kind == "lrp":                 # the slice's own pre-correction latent: the last part of its first conv
                     s = self.sup(i)
                     b = self._alloc(t1, C1, sc)
-                    ents.append(HF.sub_pack(w, hm + s, hm + s + sc, b, 0, C1, sc, False))
+                    ents.append(packs.sub_pack(w, hm + s, hm + s + sc, b, 0, C1, sc, False))
                     addr[(kind, i, "own")] = b.data_ptr()
                     keep.append(b)
                 w2, w3 = self.conv(kind, i, 1).weight, self.conv(kind, i, 2).weight
                 b2, b3 = self._alloc(t2, C2, C1), self._alloc(t3, sc, C2)
-                ents.append(HF.sub_pack(w2, 0, C1, b2, 0, C2, C1, False))
-                ents.append(HF.sub_pack(w3, 0, C2, b3, 0, sc, C2, False))
+                ents.append(packs.sub_pack(w2, 0, C1, b2, 0, C2, C1, False))
+                ents.append(packs.sub_pack(w3, 0, C2, b3, 0, sc, C2, False))
                 addr[(kind, i, "l2")], addr[(kind, i, "l3")] = b2.data_ptr(), b3.data_ptr()
                 keep += [b2, b3]
         self._fwd = (addr, ents, keep)
@@ -185,7 +186,7 @@ class CharmPlan:
             addr[name] = buf.data_ptr()
             for k in range(n):
                 kind, i = self.order[lo + k]
-                ents.append(HF.sub_pack(self.conv(kind, i, 0).weight, 0, hm, buf, k * C1, hm, C1, True, dld=n * C1, tstride=hm * n * C1))
+                ents.append(packs.sub_pack(self.conv(kind, i, 0).weight, 0, hm, buf, k * C1, hm, C1, True, dld=n * C1, tstride=hm * n * C1))
         # support parts, K-concatenated over the consumers of slice k: [t1][sc][n * C1]
         for k in range(ms):
             for half in ("mu", "sc"):
@@ -197,26 +198,26 @@ class CharmPlan:
                 keep.append(buf)
                 addr[("sup_" + half, k)] = buf.data_ptr()
                 for idx, (kind, j) in enumerate(cons):
-                    ents.append(HF.sub_pack(self.conv(kind, j, 0).weight, hm + k * sc, hm + (k + 1) * sc, buf, idx * C1, sc, C1, True,
+                    ents.append(packs.sub_pack(self.conv(kind, j, 0).weight, hm + k * sc, hm + (k + 1) * sc, buf, idx * C1, sc, C1, True,
                                             dld=n * C1, tstride=sc * n * C1))
         for kind in ("mean", "scale", "lrp"):
             for i in range(S):
                 w = self.conv(kind, i, 0).weight
                 if i == 0 and kind != "lrp":
                     b = self._alloc(t1, hm, C1)
-                    ents.append(HF.sub_pack(w, 0, hm, b, 0, hm, C1, True))
+                    ents.append(packs.sub_pack(w, 0, hm, b, 0, hm, C1, True))
                     addr[(kind, 0, "l1")] = b.data_ptr()
                     keep.append(b)
                 if kind == "lrp":
                     s = self.sup(i)
                     b = self._alloc(t1, sc, C1)
-                    ents.append(HF.sub_pack(w, hm + s, hm + s + sc, b, 0, sc, C1, True))
+                    ents.append(packs.sub_pack(w, hm + s, hm + s + sc, b, 0, sc, C1, True))
                     addr[(kind, i, "own")] = b.data_ptr()
                     keep.append(b)
                 w2, w3 = self.conv(kind, i, 1).weight, self.conv(kind, i, 2).weight
                 b2, b3 = self._alloc(t2, C1, C2), self._alloc(t3, C2, sc)
-                ents.append(HF.sub_pack(w2, 0, C1, b2, 0, C1, C2, True))
-                ents.append(HF.sub_pack(w3, 0, C2, b3, 0, C2, sc, True))
+                ents.append(packs.sub_pack(w2, 0, C1, b2, 0, C1, C2, True))
+                ents.append(packs.sub_pack(w3, 0, C2, b3, 0, C2, sc, True))
                 addr[(kind, i, "l2")], addr[(kind, i, "l3")] = b2.data_ptr(), b3.data_ptr()
                 keep += [b2, b3]
         self._bwd = (addr, ents, keep)
@@ -275,7 +276,7 @@ class CharmRun:
         self.MSL = mk(3 * self.Cy)
         self.Yh, self.Ypre = mk(self.Cy), mk(self.Cy)
         self.addr, ents, _ = P.fwd_packs()
-        HF.ensure_fresh(ents)
+        packs.ensure_fresh(ents)
         self._bias = {}
 
     # ---- views
@@ -440,7 +441,7 @@ def charm_backward(run: CharmRun, dyhat: Optional[torch.Tensor], gbits: Optional
     dev, n, h, w, M, Cy = run.dev, run.n, run.h, run.w, run.M, run.Cy
     S, ms, C1, C2, sc, hm, T = P.S, P.ms, P.C1, P.C2, P.sc, P.hm, P.T
     baddr, bents, _ = P.bwd_packs()
-    HF.ensure_fresh(bents)
+    packs.ensure_fresh(bents)
     mk = lambda c, zero=False: (torch.zeros if zero else torch.empty)((M, c), dtype=torch.float32, device=dev)
     dA1, dA2 = mk(P.NT * C1), mk(P.NT * C2)
     G4 = mk(4 * Cy)            # dMU | dSG | dLR | dy (one pixel stride for the Gaussian-conditional backward)

@@ -12,90 +12,12 @@ from typing import Optional, Tuple
 import torch
 
 from . import lib as L
-from . import ops
-
-_weights_epoch = 0
-
-
-def bump_weights_epoch() -> None:
-    """Invalidate every weight pack (parameters were modified behind torch's back by something other than an optimiser
-    that owns a PackTable -- the fused Adam refills its packs itself, see PackTable)."""
-    global _weights_epoch
-    _weights_epoch += 1
-
+from . import ops, packs
 
 def _grad_slot(p: torch.Tensor) -> torch.Tensor:
     if p.grad is None:
         p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
     return p.grad
-
-
-class _PackEntry:
-    """One persistent weight pack: destination buffer + how to refill it from its parameter.  A *sub-block* entry
-    (`src_off` / `srcJ` / `dst_off` / `dld` / `tstride`, see crdr_pack_item) packs an input-channel range of the parameter
-    into a row / column range of a wider pack shared with other parameters (the Charm's hoisted first-layer convs)."""
-    __slots__ = ("weight", "dst", "I", "J", "T", "rows", "cols", "mode", "key", "src_off", "srcJ", "dst_off", "dld", "tstride")
-
-    def __init__(self):
-        self.src_off = self.srcJ = self.dst_off = self.dld = self.tstride = 0
-
-    def item(self) -> "L.PackItem":
-        return L.PackItem(src=self.weight.data_ptr() + self.src_off, dst=self.dst.data_ptr() + self.dst_off, I=self.I, J=self.J,
-                          T=self.T, rows=self.rows, cols=self.cols, mode=self.mode, srcJ=self.srcJ, dld=self.dld,
-                          tstride=self.tstride)
-
-    def fill(self) -> None:
-        lib = L.load()
-        ops.register_persistent_pack(self.dst)
-        ops.bump_pack_version(self.dst.data_ptr())
-        if self.mode in (0, 1):
-            it = self.item()
-            L.check(lib.crdr_pack_weight_item(C.byref(it), ops._stream()), "pack_weight_item")
-        else:
-            L.check(lib.crdr_pack_weight(self.weight.data_ptr(), self.dst.data_ptr(), self.I, self.J, self.T, self.rows, self.cols,
-                                         self.mode, ops._stream()), "pack_weight")
-
-
-def sub_pack(weight: torch.Tensor, j0: int, j1: int, dst: torch.Tensor, dst_off: int, rows: int, cols: int, transposed: bool,
-             dld: int = 0, tstride: int = 0) -> _PackEntry:
-    """Register a sub-block pack: input channels [j0, j1) of `weight` [I][J][kh][kw] -> the [T][rows][cols] block that
-    starts `dst_off` floats into `dst` (row stride `dld`, tap stride `tstride`; 0 = dense).  transposed=False: pack row =
-    output channel i, column = input channel j (forward operand); True: row = j, column = i (input-gradient operand)."""
-    global _pack_serial
-    ops._require_gpu(weight)
-    assert weight.is_contiguous() and weight.dim() == 4
-    e = _PackEntry()
-    e.key = None
-    e.weight = weight.detach()
-    e.I, e.J, e.T = weight.shape[0], j1 - j0, weight.shape[2] * weight.shape[3]
-    e.src_off, e.srcJ = 4 * j0 * e.T, weight.shape[1]
-    e.mode = 1 if transposed else 0
-    e.rows, e.cols = rows, cols
-    assert rows % 8 == 0 and cols % 32 == 0 and rows >= (e.J if transposed else e.I) and cols >= (e.I if transposed else e.J)
-    e.dst, e.dst_off, e.dld, e.tstride = dst, 4 * dst_off, dld, tstride
-    ops.register_persistent_pack(dst)
-    _pack_entries.append(e)
-    _pack_serial += 1
-    return e
-
-
-def ensure_fresh(entries) -> None:
-    """Refill the entries whose parameter changed since their last fill (first use, load_state_dict, a foreign optimiser);
-    the fused Adam keeps them fresh through its PackTable."""
-    for e in entries:
-        k = _current_key(e.weight)
-        if e.key != k:
-            e.fill()
-            e.key = k
-
-
-PACK_MISS_LOG = {} if __import__("os").environ.get("CRDR_DEBUG_PACK") == "1" else None  # {(I, J, T, mode, why): count}
-_pack_entries = []   # every pack ever made, in creation order (PackTable selects the ones of one optimiser)
-_pack_serial = 0     # bumped when _pack_entries grows
-
-
-def _current_key(w: torch.Tensor):
-    return (w.data_ptr(), w._version, _weights_epoch)
 
 
 class ConvSpec:
@@ -129,38 +51,13 @@ class ConvSpec:
         return self._pack(weight, "scatter", 3)
 
     def _pack(self, weight: torch.Tensor, slot, mode: int) -> torch.Tensor:
-        global _pack_serial
         ent = self._packs.get(slot)
-        key = _current_key(weight)
-        if ent is not None and ent.key == key:
-            return ent.dst
         if ent is None or ent.weight.data_ptr() != weight.data_ptr() or ent.weight.shape != weight.shape:
-            ops._require_gpu(weight)
-            assert weight.is_contiguous()
-            ent = _PackEntry()
-            ent.key = None
-            ent.weight = weight.detach()
-            ent.I, ent.J = weight.shape[0], weight.shape[1]
-            ent.T = weight.shape[2] * weight.shape[3] if weight.dim() == 4 else 1
-            ent.mode = mode
-            if mode == 2:
-                shape = (1, ops.round32(ent.I), ops.round32(4 * ent.T))
-            elif mode == 3:
-                shape = (1, ops.round32(4 * ent.T), ops.round32(ent.I))
-            else:
-                shape = (ent.T, ops.round32(ent.J), ops.round32(ent.I)) if mode else (ent.T, ops.round32(ent.I), ops.round32(ent.J))
-            ent.rows, ent.cols = shape[1], shape[2]
-            ent.dst = torch.empty(shape, dtype=torch.float32, device=weight.device)
-            ops.register_persistent_pack(ent.dst)
-            self._packs[slot] = ent
-            _pack_entries.append(ent)
-            _pack_serial += 1
-        if PACK_MISS_LOG is not None:
-            why = "new" if ent.key is None else "ptr" if ent.key[0] != key[0] else "version" if ent.key[1] != key[1] else "epoch"
-            k = (ent.I, ent.J, ent.T, ent.mode, why)
-            PACK_MISS_LOG[k] = PACK_MISS_LOG.get(k, 0) + 1
-        ent.fill()
-        ent.key = key
+            I, J, r = weight.shape[0], weight.shape[1], ops.round32
+            T = weight.shape[2] * weight.shape[3] if weight.dim() == 4 else 1
+            shape = {0: (T, r(I), r(J)), 1: (T, r(J), r(I)), 2: (1, r(I), r(4 * T)), 3: (1, r(4 * T), r(I))}[mode]   # (modes: crdr_pack_item)
+            ent = self._packs[slot] = packs._PackEntry(weight, torch.empty(shape, dtype=torch.float32, device=weight.device), mode, shape[1], shape[2])
+        packs.ensure_fresh((ent,), log=True)
         return ent.dst
 
 
@@ -178,64 +75,6 @@ def scatter_conv(u: torch.Tensor, weight: torch.Tensor, bias, spec: "ConvSpec", 
                                 None if bias is None else bias.data_ptr(), out.data_ptr(), ops.ld_for(c), out_hw[0], out_hw[1], c,
                                 ops._stream()), "col2im_rgb")
     return out
-
-
-class PackTable:
-    """The packs whose parameter lives in one address range (an optimiser's flat buffer, or a partition of it), refilled
-    by ONE launch right after that optimiser's update -- instead of one small launch per layer on next use.
-
-    Its batched.JobTable is rewritten in place when new packs appear, also under a graph that replays it
-    (frozen_after_capture=False, see batched): the captured launch keeps covering everything."""
-    CAP = 4096
-
-    def __init__(self, flat: torch.Tensor, lo: int = 0, hi: Optional[int] = None):
-        hi = flat.numel() if hi is None else hi
-        self.lo, self.hi = flat.data_ptr() + 4 * lo, flat.data_ptr() + 4 * hi
-        self.device = flat.device
-        self.table = ops.JobTable(flat.device, L.PackItem, self.CAP, name="PackTable")
-        self.entries, self.singles = [], []
-        self.filters = None
-        self._seen = -1
-
-    def _refresh(self) -> None:
-        if self._seen == _pack_serial:
-            return
-        mine = [e for e in _pack_entries if self.lo <= e.weight.data_ptr() < self.hi and e.dst.device == self.device]
-        ents = [e for e in mine if e.mode in (0, 1) and e.T <= 32]   # what the batched kernel takes
-        self.table.upload([e.item() for e in ents], lambda it: (it.rows // 8) * (it.cols // 32))
-        self.entries, self.singles = ents, [e for e in mine if not (e.mode in (0, 1) and e.T <= 32)]
-        self._seen = _pack_serial
-
-    def refill(self) -> None:
-        """Refill every pack of the range from the current parameter values and mark them fresh."""
-        self._refresh()
-        for ptr in {e.dst.data_ptr() for e in self.entries}:
-            ops.bump_pack_version(ptr)
-        if self.entries:
-            lib = L.load()
-            L.check(lib.crdr_pack_weights_batched(*self.table.operands, ops._stream()), "pack_weights_batched")
-        for e in self.singles:
-            e.fill()
-        for e in self.entries + self.singles:
-            e.key = _current_key(e.weight)
-        # ... and, behind the packs, every transformed-filter cache of the F(4x4) kernel derived from them: one launch (ops.FilterTable)
-        if self.filters is None:
-            self.filters = ops.FilterTable(self.device)
-        self.filters.refill({e.dst.data_ptr() for e in self.entries + self.singles})
-        if torch.cuda.is_current_stream_capturing():
-            ops.on_replay(self._replayed)   # (trainer/graphs.py: a replay runs these launches without this method)
-
-    def _replayed(self) -> None:
-        """The graph that captured refill() has just been replayed: refill()'s host-side bookkeeping without its launches.  The packs and the
-        filter caches in the device tables AS THE REPLAYED LAUNCHES SAW THEM are fresh; packs / caches that appeared since (an eager
-        validation pass at another image size, say) join the tables now and are covered from the next replay on -- until then their own
-        staleness checks (pack keys, version stamps) make their launches refill / re-transform."""
-        rewritten = {e.dst.data_ptr() for e in self.entries + self.singles}
-        for ptr in rewritten:
-            ops.bump_pack_version(ptr)
-        if self.filters is not None:
-            self.filters.replayed(rewritten)
-        self._refresh()
 
 
 def _flags(bias, act, vec2, res, gate, affine) -> int:

@@ -14,7 +14,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import lib as L
-from .batched import BumpArena, JobTable, SiteTables  # noqa: F401  (the capture rules of the batched launches live there)
+from . import packs
+from .batched import BumpArena, JobTable, SiteTables, _capturing, _require_gpu, _stream  # noqa: F401  (the capture rules of the batched launches live there)
 
 _ws_cache = {}
 _ws_keep = []   # superseded buffers stay alive: captured graphs may still reference them
@@ -148,166 +149,6 @@ def _wgrad_wino4_ids():
     return [tile_id(w4 - 1, ls) for ls in range(9)] if WINOGRAD and WINO4 and w4 >= 0 else []
 
 
-# Transformed filters of the F(4x4) Winograd kernel as PERSISTENT packs (round 5).  A launch that runs that kernel on registered weight packs
-# (functional._PackEntry.dst: buffers that live as long as their layer and are refilled in place) keeps its transformed filters in a tensor of
-# its own, keyed by (pack addresses, descriptor, algorithm) and stamped with the packs' version counters: a later launch with the same key
-# whose packs still carry those versions skips the transform (crdr_conv2d_grouped_ex, filter_cache_valid = 1); if any writer has touched a
-# pack since (bump_pack_version -- every writer bumps), the launch re-transforms into the same tensor.  The packs of an optimiser are
-# refilled by ONE launch behind its update (functional.PackTable.refill); refill_filters() then rebuilds every filter cache derived from
-# them with ONE more launch (crdr_w4_filters_batched) and stamps them current -- so inside a training step no convolution launch
-# transforms anything (round 4: 80.8 transform launches, 2.1 ms per stage-3 step; the generator's second forward pass and the
-# discriminator's passes reused filters only inside an explicit `filter_scope`).
-# Under graph capture nothing new is cached (a tensor born inside a capture belongs to that graph's pool): a launch whose cache does not
-# exist yet transforms into the workspace as before; the warm-up iterations in front of every capture create the caches.
-FILTER_SCOPE_STATS = {"filled": 0, "reused": 0, "batched": 0}
-_persistent_packs = {}   # data_ptr -> weakref of a persistent weight-pack buffer (functional._PackEntry.dst): only those are cached by address
-_pack_versions = {}      # data_ptr -> how often that buffer was (re)written: every writer of a registered pack bumps it (bump_pack_version)
-_filter_cache = {}       # key -> _FilterCache
-_filter_serial = [0]     # bumped when _filter_cache grows (FilterTable re-reads it)
-
-
-class _FilterCache:
-    __slots__ = ("u", "wkeys", "versions", "item", "nbytes", "packs", "tick")
-
-    def alive(self) -> bool:
-        """every pack this cache was derived from still lives at its address (a dead pack's address may be handed to a new, differently
-        shaped tensor: a cache keyed by that address must never be rebuilt from it)"""
-        return all((r() is not None and r().data_ptr() == p_) for r, p_ in zip(self.packs, self.wkeys))
-
-
-# Host-side bookkeeping that a captured HIP graph skips on replay (trainer/graphs.py): code that runs under capture and keeps host state in
-# step with what its launches do on the device -- functional.PackTable.refill bumps pack versions and stamps the filter caches its batched
-# launch rebuilds -- registers a callable here; SegmentGraphs.run collects them per captured segment and calls them after every replay.
-REPLAY_HOOKS = None
-
-
-def on_replay(fn) -> None:
-    if REPLAY_HOOKS is not None and fn not in REPLAY_HOOKS:
-        REPLAY_HOOKS.append(fn)
-
-
-FILTER_CACHE_BUDGET = int(os.environ.get("CRDR_FILTER_CACHE_GB", "24")) << 30   # bytes of transformed filters kept (least recently used go first)
-_filter_tick = [0]
-
-
-def _drop_dead_filter_caches() -> None:
-    dead = [k for k, e in _filter_cache.items() if not e.alive()]
-    for k in dead:
-        del _filter_cache[k]
-    if dead:
-        _filter_serial[0] += 1
-
-
-def _evict_filter_caches(need: int) -> None:
-    """Keep the caches within FILTER_CACHE_BUDGET: the least recently launched ones go first (never under graph capture; a cache a captured
-    graph launches with stays referenced by that graph's FilterTable entries and is simply re-created on its next eager use)."""
-    total = sum(e.nbytes for e in _filter_cache.values()) + need
-    if total <= FILTER_CACHE_BUDGET:
-        return
-    for k, e in sorted(_filter_cache.items(), key=lambda kv: kv[1].tick):
-        if total <= FILTER_CACHE_BUDGET:
-            break
-        total -= e.nbytes
-        del _filter_cache[k]
-    _filter_serial[0] += 1
-
-
-def register_persistent_pack(t: torch.Tensor) -> None:
-    import weakref
-    old = _persistent_packs.get(t.data_ptr())
-    if old is not None and old() is not t:   # the address of a pack that died: what was derived from the old content is void
-        bump_pack_version(t.data_ptr())
-        for k in [k for k, e in _filter_cache.items() if t.data_ptr() in e.wkeys]:
-            del _filter_cache[k]
-        _filter_serial[0] += 1
-    _persistent_packs[t.data_ptr()] = weakref.ref(t)
-    _pack_versions.setdefault(t.data_ptr(), 0)
-
-
-def bump_pack_version(ptr: int) -> None:
-    """The pack buffer at `ptr` is being rewritten in place (functional._PackEntry.fill, PackTable.refill, or any future writer): whatever
-    was derived from its previous content is stale from here on."""
-    _pack_versions[ptr] = _pack_versions.get(ptr, 0) + 1
-
-
-def pack_version(ptr: int) -> int:
-    return _pack_versions.get(ptr, 0)
-
-
-def filter_cache_bytes() -> int:
-    return sum(e.nbytes for e in _filter_cache.values())
-
-
-def filter_scope_invalidate(ptr=None) -> None:
-    """Drop the filter caches derived from the pack at `ptr` (all of them: None).  Not needed for correctness -- the version stamps decide --
-    but it frees the memory of caches whose pack is gone."""
-    for k in [k for k, e in _filter_cache.items() if ptr is None or ptr in e.wkeys]:
-        del _filter_cache[k]
-    _filter_serial[0] += 1
-
-
-def _is_persistent_pack(ptr: int) -> bool:
-    r = _persistent_packs.get(ptr)
-    t = r() if r is not None else None
-    return t is not None and t.data_ptr() == ptr
-
-
-class filter_scope:
-    """Kept for callers of rounds 3-4 (the trainer wrapped the generator's two forward passes in one): the caches are persistent now and
-    valid by version, inside or outside a scope; entering / leaving changes nothing."""
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-class FilterTable:
-    """The filter caches derived from a set of weight packs (an optimiser's), rebuilt by one launch.  Its batched.JobTable is rewritten in place
-    when new caches appear, also under a graph that replays it (frozen_after_capture=False): the captured launch keeps covering everything."""
-    CAP = 1024
-
-    def __init__(self, device):
-        self.device = device
-        self.table = JobTable(device, L.W4FilterItem, self.CAP, name="FilterTable")
-        self.entries = []
-        self._seen = -1
-        self._packs = frozenset()
-
-    def _refresh(self, pack_ptrs) -> None:
-        pack_ptrs = frozenset(pack_ptrs)
-        if self._seen == _filter_serial[0] and pack_ptrs == self._packs:
-            return
-        if not torch.cuda.is_current_stream_capturing():
-            _drop_dead_filter_caches()
-        ents = [e for e in _filter_cache.values() if e.u.device == self.device and e.alive() and all(p_ in pack_ptrs for p_ in e.wkeys)]
-        if len(ents) > self.CAP:   # more caches than the device table holds: the most recently used stay in the batched rebuild, the others
-            ents = sorted(ents, key=lambda e: -e.tick)[:self.CAP]   # fall behind their packs' versions and re-transform inside their launches
-            ents.sort(key=lambda e: e.tick)
-        self.table.upload([e.item for e in ents], lambda it: int(it.units))
-        self.entries = ents
-        self._seen, self._packs = _filter_serial[0], pack_ptrs
-
-    def refill(self, pack_ptrs) -> None:
-        """Rebuild every cache derived from `pack_ptrs` (just refilled) and stamp it with the packs' current versions."""
-        self._refresh(pack_ptrs)
-        if self.entries:
-            lib = L.load()
-            L.check(lib.crdr_w4_filters_batched(*self.table.operands, _stream()), "w4_filters_batched")
-            FILTER_SCOPE_STATS["batched"] += len(self.entries)
-            for e in self.entries:
-                e.versions = tuple(pack_version(p_) for p_ in e.wkeys)
-
-    def replayed(self, pack_ptrs) -> None:
-        """A captured graph holding this table's rebuild launch has just been replayed (the packs' versions were bumped by the caller): the
-        caches in the table AS THE LAUNCH SAW IT are current; caches that appeared since join the table now, are rebuilt from the next replay
-        on, and until then stay behind their packs' versions (their launches re-transform)."""
-        for e in self.entries:
-            e.versions = tuple(pack_version(p_) for p_ in e.wkeys)
-        self._refresh(pack_ptrs)
-
-
 # Test hook: callable(weight, saved activation as an NCHW view, offset vector or None) called in grad mode by every fused conv / chain layer /
 # Charm transform with a ReLU epilogue -- the activations the product's backward derives its ReLU masks from (CRDR_EPI_RELUMASK: act > 0;
 # with CRDR_EPI_MASKOFF, where a beta vector was added after the ReLU: act - offset > 0).  tests/test_gpu_step.py hands the generator's masks
@@ -334,42 +175,12 @@ def _demote_if_misaligned(d, ios, G: int, explicit: bool) -> None:
 
 
 def _launch_conv(lib, d, ios, G: int, ws, ws_n, device):
-    """crdr_conv2d_grouped, through the persistent filter cache where the launch runs the F(4x4) kernel on registered weight packs."""
-    if (d.reserved & 0xFF) == _ids().wino4 and all(_is_persistent_pack(int(ios[g].w)) for g in range(G)):
-        # (the key leaves the K-split bits of the algorithm id out on purpose: the block layout of the transformed filters does not depend
-        # on the split count -- wino4_filter_bytes / wino4_filter_thread take no nsplit)
-        wk = tuple(int(ios[g].w) for g in range(G))
-        key = (wk, G, d.reserved & 0xFF, d.N, d.H, d.W, d.C, d.OH, d.OW, d.OC, d.kh, d.kw, d.stride, d.pad, d.transposed, d.wrows, d.wcols)
-        ent = _filter_cache.get(key)
-        if ent is not None and not ent.alive():   # (a pack died and its address was reused: drop, never trust)
-            del _filter_cache[key]
-            _filter_serial[0] += 1
-            ent = None
-        if ent is None and not torch.cuda.is_current_stream_capturing():
-            nb = int(lib.crdr_conv2d_filter_cache_bytes(C.byref(d), G))
-            if nb:
-                _evict_filter_caches(nb)
-                ent = _FilterCache()
-                ent.u = torch.empty(nb // 4, dtype=torch.float32, device=device)
-                ent.wkeys, ent.versions, ent.nbytes = wk, None, nb
-                ent.packs = tuple(_persistent_packs[p_] for p_ in wk)
-                ent.tick = 0
-                ent.item = L.W4FilterItem()
-                L.check(lib.crdr_conv2d_filter_item(C.byref(d), G, C.byref(ent.item)), "conv2d_filter_item")
-                for g in range(G):
-                    ent.item.w[g] = wk[g]
-                ent.item.u = ent.u.data_ptr()
-                _filter_cache[key] = ent
-                _filter_serial[0] += 1
-        if ent is not None:
-            _filter_tick[0] += 1
-            ent.tick = _filter_tick[0]
-            vers = tuple(pack_version(p_) for p_ in wk)
-            valid = ent.versions == vers   # derived from the packs' CURRENT content, not merely from the same addresses
-            ent.versions = vers
-            FILTER_SCOPE_STATS["reused" if valid else "filled"] += 1
-            return lib.crdr_conv2d_grouped_ex(C.byref(d), ios, G, ws, ws_n, ent.u.data_ptr(), ent.nbytes, int(valid), _stream())
-    return lib.crdr_conv2d_grouped(C.byref(d), ios, G, ws, ws_n, _stream())
+    """crdr_conv2d_grouped, through the persistent filter cache (packs) where the launch runs the F(4x4) kernel on registered weight packs."""
+    cached = packs.filter_cache_for(d, ios, G, device) if (d.reserved & 0xFF) == _ids().wino4 else None
+    if cached is None:
+        return lib.crdr_conv2d_grouped(C.byref(d), ios, G, ws, ws_n, _stream())
+    ent, valid = cached
+    return lib.crdr_conv2d_grouped_ex(C.byref(d), ios, G, ws, ws_n, ent.u.data_ptr(), ent.nbytes, int(valid), _stream())
 
 
 # Tuner trials of the F(4x4) kernel: in the step its transformed filters are rebuilt once per optimiser update by the batched launch, not in
@@ -388,12 +199,11 @@ def _tune_conv_launch(lib, d, ios, G: int, device) -> bool:
     _tune_w4_penalty[0] = 0.0
     w_, wn_ = _conv_workspace(lib, d, G, device)
     nb = int(lib.crdr_conv2d_filter_cache_bytes(C.byref(d), G)) if (d.reserved & 0xFF) == _ids().wino4 else 0
-    wk = tuple(int(ios[g].w) for g in range(G))
-    if not nb or not all(_is_persistent_pack(p_) for p_ in wk) or torch.cuda.is_current_stream_capturing():
+    if not nb or not packs.cacheable(ios, G) or _capturing():
         # (no transformed filters, or) the real launch will not find a cache (sub-block / temporary packs, or a launch first seen under
         # capture): it transforms on every call, and that is what the candidate is timed with
         return lib.crdr_conv2d_grouped(C.byref(d), ios, G, w_, wn_, _stream()) == 0
-    key = (wk, tuple(pack_version(p_) for p_ in wk), G, d.N, d.H, d.W, d.C, d.OH, d.OW, d.OC, d.kh, d.kw, d.stride, d.pad, d.transposed, d.wrows, d.wcols)
+    key = (packs.filter_key(d, ios, G), tuple(packs.version(int(ios[g].w)) for g in range(G)))
     ent = _tune_filters.get(key)
     if ent is None or ent.numel() * 4 < nb:
         _tune_filters.clear()   # (one shape is tuned at a time: the previous shape's scratch is garbage)
@@ -544,10 +354,6 @@ def _prof_end(kind: str, flops: float, e0, label: str = "", nbytes: float = 0.0)
     PROFILE.setdefault(kind, []).append((flops, e0, e1, label, nbytes))
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
 _WS_HEAD = 4 * 16384  # bytes at the head of every scratch buffer: the split-K tickets of the conv kernels (CRDR_CONV_TICKETS int32)
 
 
@@ -585,13 +391,6 @@ def reserve_workspace(device, stream: "torch.cuda.Stream") -> None:
         if buf is not None:
             _ws_keep.append(buf)
         _ws_cache[key] = torch.zeros(need, dtype=torch.uint8, device=dev)
-
-
-def _require_gpu(t: torch.Tensor):
-    if not t.is_cuda:
-        raise L.CrdrHipError("crdr_amd ops run on the HIP device only (got a CPU tensor); there is no CPU fallback")
-    if t.dtype != torch.float32:
-        raise L.CrdrHipError(f"crdr_amd ops are fp32 (got {t.dtype})")
 
 
 def nhwc(t: torch.Tensor) -> Tuple[torch.Tensor, int]:

@@ -15,8 +15,7 @@ from typing import Callable, Dict, Hashable
 
 import torch
 
-from crdr_amd.hip import functional as HF
-from crdr_amd.hip import ops
+from crdr_amd.hip import batched, ops
 
 
 class SegmentGraphs:
@@ -56,12 +55,12 @@ class SegmentGraphs:
             dbg = os.environ.get("CRDR_DEBUG_DIST", "0") == "1"
             if dbg:
                 print(f"[graphs] capture begin {key} stream={self._stream.cuda_stream:#x}", flush=True)
-            ops.REPLAY_HOOKS = hooks = []
+            batched.REPLAY_HOOKS = hooks = []
             try:
                 with torch.cuda.graph(g, pool=self._pool, stream=self._stream, capture_error_mode=mode):
                     out = fn()
             finally:
-                ops.REPLAY_HOOKS = None
+                batched.REPLAY_HOOKS = None
             self._hooks[key] = hooks
             fresh = True
             if dbg:
@@ -70,7 +69,7 @@ class SegmentGraphs:
             self._graphs[key] = g
             self._outs[key] = out
         g.replay()
-        if not fresh:   # host-side bookkeeping of the code the graph replaced (ops.on_replay): on the capture pass that code itself ran
+        if not fresh:   # host-side bookkeeping of the code the graph replaced (batched.on_replay): on the capture pass that code itself ran
             for h in self._hooks.get(key, ()):
                 h()
         return self._outs[key]

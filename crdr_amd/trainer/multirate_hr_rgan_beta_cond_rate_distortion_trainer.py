@@ -21,7 +21,6 @@ import numpy as np
 import torch
 
 from crdr_amd.hip import chain as _chain
-from crdr_amd.hip import ops as _ops
 from crdr_amd.utils.registry import TRAINER_REGISTRY
 
 from . import dist as D
@@ -59,12 +58,6 @@ class MultirateBetaCondHrrGanRateDistortionTrainer(MultirateHighRateRGANRateDist
 
     # ------------------------------------------------------------------ G phase: forward, losses, backward
     def _g_forward(self, real, cond: Dict, noise, current_iter: int) -> Dict:
-        # (no parameter changes inside: the generator and the discriminator run twice each on the same weights, and the second pass
-        # reuses the Winograd-transformed filters of the first)
-        with _ops.filter_scope():
-            return self._g_forward_body(real, cond, noise, current_iter)
-
-    def _g_forward_body(self, real, cond: Dict, noise, current_iter: int) -> Dict:
         q, beta_t = cond["rate_ind"], self._beta_t
         self.discriminator.requires_grad_(False)
         self.g_optimizer.zero_grad()

@@ -11,9 +11,9 @@ from typing import Dict, Iterable, List, Optional
 
 import torch
 
-from crdr_amd.hip import functional as HF
 from crdr_amd.hip import lib as L
 from crdr_amd.hip import ops
+from crdr_amd.hip import packs
 from crdr_amd.utils.registry import OPTIMIZER_REGISTRY, SCHEDULER_REGISTRY
 
 
@@ -173,7 +173,7 @@ class Adam:
             g["step"] = max(pt["step"] for pt in g["parts"])
         for g, pt in touched:
             if pt.get("packs") is None:
-                pt["packs"] = HF.PackTable(g["flat"], pt["lo"], pt["hi"])
+                pt["packs"] = packs.PackTable(g["flat"], pt["lo"], pt["hi"])
             pt["packs"].refill()
 
     def host_step_counts(self) -> None:
@@ -228,7 +228,7 @@ class Adam:
                     pt["dyn"][1:2].fill_(float(pt["step"]))
                     pt["dyn"][0:1].fill_(float(g["lr"]))
                     pt["dyn_lr"] = float(g["lr"])
-            HF.bump_weights_epoch()
+            packs.bump_weights_epoch()
 
 
 class MultiStepLR:

@@ -444,41 +444,147 @@ def test_winograd_ids_are_planned_only_for_the_shapes_they_take(lib):
     assert lib.crdr_conv2d_wgrad_workspace(C.byref(wdesc(3, 2))) == 0
 
 
-def test_filter_cache_bookkeeping():
-    """ops' persistent filter caches (host side only, no launches): only registered persistent packs count as cacheable, a registration dies
-    with its tensor, every writer of a pack bumps its version, filter_scope is a no-op kept for older callers, and dropping the caches of a
-    pack drops exactly those"""
-    import torch
-    from crdr_amd.hip import ops
-    a, b = torch.zeros(64), torch.zeros(64)
-    assert not ops._is_persistent_pack(a.data_ptr())
-    ops.register_persistent_pack(a)
-    assert ops._is_persistent_pack(a.data_ptr()) and not ops._is_persistent_pack(b.data_ptr())
-    v0 = ops.pack_version(a.data_ptr())
-    ops.bump_pack_version(a.data_ptr())
-    assert ops.pack_version(a.data_ptr()) == v0 + 1 and ops.pack_version(b.data_ptr()) == 0
-    keep = dict(ops._filter_cache)
+def _fake_filter_cache(packs, ptrs, u, nbytes=0, tick=0, item=None):
+    e = packs._FilterCache()
+    e.packs, e.u, e.versions, e.item, e.nbytes, e.tick = tuple(packs._record(p) for p in ptrs), u, None, item, nbytes, tick
+    packs._filter_cache[(tuple(ptrs), len(ptrs), 37, u if isinstance(u, str) else id(u))] = e
+    return e
+
+
+@pytest.fixture
+def filter_caches():
+    """crdr_amd.hip.packs with an empty filter-cache dictionary and the default budget, both put back afterwards"""
+    from crdr_amd.hip import packs
+    keep, budget = dict(packs._filter_cache), packs.FILTER_CACHE_BUDGET
+    packs._filter_cache.clear()
     try:
-        ops._filter_cache.clear()
-        for name, wk in (("Ua", (a.data_ptr(),)), ("Uab", (a.data_ptr(), b.data_ptr())), ("Ub", (b.data_ptr(),))):
-            e = ops._FilterCache()
-            e.wkeys, e.u, e.versions, e.item, e.nbytes = wk, name, None, None, 0
-            ops._filter_cache[(wk, len(wk), 37)] = e
-        with ops.filter_scope():
-            with ops.filter_scope():
-                assert len(ops._filter_cache) == 3
-        serial = ops._filter_serial[0]
-        ops.filter_scope_invalidate(a.data_ptr())
-        assert [e.u for e in ops._filter_cache.values()] == ["Ub"] and ops._filter_serial[0] > serial
-        ops.filter_scope_invalidate()
-        assert ops._filter_cache == {}
+        yield packs
     finally:
-        ops._filter_cache.clear()
-        ops._filter_cache.update(keep)
+        packs._filter_cache.clear()
+        packs._filter_cache.update(keep)
+        packs.FILTER_CACHE_BUDGET = budget
+
+
+def test_filter_cache_bookkeeping(filter_caches):
+    """packs' persistent filter caches (host side only, no launches): only registered persistent packs count as cacheable, a registration dies
+    with its tensor, every writer of a pack bumps its version, and dropping the caches of a pack drops exactly those"""
+    packs = filter_caches
+    a, b = torch.zeros(64), torch.zeros(64)
+    assert not packs.is_persistent(a.data_ptr())
+    packs.register(a)
+    assert packs.is_persistent(a.data_ptr()) and not packs.is_persistent(b.data_ptr())
+    v0 = packs.version(a.data_ptr())
+    packs.bump_version(a.data_ptr())
+    assert packs.version(a.data_ptr()) == v0 + 1 and packs.version(b.data_ptr()) == 0
+    for name, wk in (("Ua", (a.data_ptr(),)), ("Uab", (a.data_ptr(), b.data_ptr())), ("Ub", (b.data_ptr(),))):
+        _fake_filter_cache(packs, wk, name)
+    assert len(packs._filter_cache) == 3
+    serial = packs._filter_serial
+    packs.drop_filter_caches(a.data_ptr())
+    assert [e.u for e in packs._filter_cache.values()] == ["Ub"] and packs._filter_serial > serial
+    packs.drop_filter_caches()
+    assert packs._filter_cache == {}
     ptr = a.data_ptr()
     del a
-    assert not ops._is_persistent_pack(ptr)
+    assert not packs.is_persistent(ptr)
 
+
+def test_registering_another_tensor_at_a_known_address_voids_what_was_derived(filter_caches):
+    """address reuse, simulated by a second tensor object over the same storage: the version is bumped, the caches derived from that address
+    are gone (the others stay) and the serial advances; registering the same tensor again changes nothing"""
+    packs = filter_caches
+    a, other = torch.zeros(64), torch.zeros(64)
+    packs.register(a)
+    packs.register(other)
+    _fake_filter_cache(packs, (a.data_ptr(),), "Ua")
+    _fake_filter_cache(packs, (other.data_ptr(),), "Uother")
+    v0, serial = packs.version(a.data_ptr()), packs._filter_serial
+    packs.register(a)
+    assert (packs.version(a.data_ptr()), packs._filter_serial, len(packs._filter_cache)) == (v0, serial, 2)
+    view = a.view(8, 8)
+    assert view is not a and view.data_ptr() == a.data_ptr()
+    packs.register(view)
+    assert packs.version(a.data_ptr()) == v0 + 1
+    assert [e.u for e in packs._filter_cache.values()] == ["Uother"] and packs._filter_serial > serial
+    assert packs.is_persistent(a.data_ptr())
+    del view
+    assert not packs.is_persistent(a.data_ptr()), "the registration belongs to the tensor registered last"
+    assert packs.version(a.data_ptr()) == v0 + 1, "a version outlives its tensor"
+
+
+def test_filter_cache_eviction_takes_the_least_recently_launched(filter_caches):
+    """a budget that holds exactly two of three caches: room for a fourth is made by dropping the lowest tick first, then the next; a request
+    that fits drops nothing"""
+    packs = filter_caches
+    a = torch.zeros(64)
+    packs.register(a)
+    for name, nbytes, tick in (("U1", 300, 5), ("U2", 100, 3), ("U3", 200, 9)):
+        _fake_filter_cache(packs, (a.data_ptr(),), name, nbytes=nbytes, tick=tick)
+    assert packs.filter_cache_bytes() == 600
+    packs.FILTER_CACHE_BUDGET = 700
+    serial = packs._filter_serial
+    packs._evict_filter_caches(100)   # 600 + 100 fits
+    assert len(packs._filter_cache) == 3 and packs._filter_serial == serial
+    packs.FILTER_CACHE_BUDGET = 500   # holds U1 + U3 or U1 + U2, not all three
+    packs._evict_filter_caches(0)
+    assert sorted(e.u for e in packs._filter_cache.values()) == ["U1", "U3"] and packs._filter_serial > serial   # tick 3 went
+    packs._evict_filter_caches(250)   # a fourth cache: 500 + 250 > 500, dropping tick 5 (300 bytes) is enough
+    assert [e.u for e in packs._filter_cache.values()] == ["U3"]
+    packs._evict_filter_caches(300)
+    assert [e.u for e in packs._filter_cache.values()] == ["U3"], "200 + 300 fits: nothing goes"
+
+
+def test_filter_table_selects_by_pack_set_and_follows_replays(filter_caches):
+    """packs.FilterTable on a CPU device: of caches on packs {a}, {a, b} and {c} a table for {a, b} takes the first two, in tick order; an
+    unchanged serial and pack set is not uploaded again; after a replay the entries carry their packs' current versions and a cache created
+    since joins the table"""
+    from crdr_amd.hip import lib as L
+    packs = filter_caches
+    a, b, c = torch.zeros(64), torch.zeros(64), torch.zeros(64)
+    for t in (a, b, c):
+        packs.register(t)
+    u = torch.zeros(4)
+
+    def cache(ptrs, tick):
+        item = L.W4FilterItem(G=len(ptrs), units=tick)
+        for g, p in enumerate(ptrs):
+            item.w[g] = p
+        return _fake_filter_cache(packs, ptrs, u.clone(), nbytes=16, tick=tick, item=item)
+    e_c, e_a, e_ab = cache((c.data_ptr(),), 1), cache((a.data_ptr(),), 2), cache((a.data_ptr(), b.data_ptr()), 7)
+    packs._filter_serial += 1   # (what creating a cache in a launch does)
+    mine = {a.data_ptr(), b.data_ptr()}
+    table = packs.FilterTable(torch.device("cpu"))
+    table._refresh(mine)
+    assert table.entries == [e_a, e_ab]
+    assert table.table._host == b"".join(bytes(e.item) for e in table.entries) and int(table.table.meta[0]) == 2
+    host = table.table._host
+    table._refresh(set(mine))
+    assert table.table._host is host, "an unchanged serial and pack set uploaded again"
+    packs.bump_version(a.data_ptr())
+    packs.bump_version(b.data_ptr())
+    e_new = cache((b.data_ptr(),), 11)
+    packs._filter_serial += 1
+    assert e_a.versions is None and e_ab.versions is None
+    table.replayed(mine)
+    assert e_a.versions == (packs.version(a.data_ptr()),) and e_ab.versions == (packs.version(a.data_ptr()), packs.version(b.data_ptr()))
+    assert table.entries == [e_a, e_ab, e_new] and int(table.table.meta[0]) == 3
+    assert e_new.versions is None, "a cache the replayed launch did not cover was stamped current"
+
+
+def test_filter_key_names_the_geometry_and_ignores_the_split_bits():
+    """packs.filter_key: the K-split bits of the algorithm id (bits 8..) do not enter; every geometry field, the pack addresses and G do"""
+    from crdr_amd.hip import lib as L
+    from crdr_amd.hip import packs
+    fields = dict(N=2, H=16, W=64, C=96, OH=16, OW=64, OC=64, kh=3, kw=3, stride=1, pad=1, transposed=0, wrows=64, wcols=96)
+    ios = (L.ConvIO * 2)(L.ConvIO(w=4096), L.ConvIO(w=8192))
+    base = packs.filter_key(L.ConvDesc(reserved=38, **fields), ios, 1)
+    assert base == packs.filter_key(L.ConvDesc(reserved=38 | (5 << 8), **fields), ios, 1)
+    assert (base.packs, base.G, base.algo, base.N, base.wcols) == ((4096,), 1, 38, 2, 96)
+    seen = {base}
+    for name in fields:
+        seen.add(packs.filter_key(L.ConvDesc(reserved=38, **{**fields, name: fields[name] + 1}), ios, 1))
+    seen.add(packs.filter_key(L.ConvDesc(reserved=38, **fields), ios, 2))
+    assert len(seen) == len(fields) + 2, "two launches that differ in a geometry field or in G share a key"
 
 
 def test_merge_tune_db_keeps_the_winograd_class(tmp_path):

@@ -75,7 +75,7 @@ def test_preadd_mask_grouped_conv():
 def test_sub_block_packs_and_hoisted_conv():
     """Three convs 64(+32k) -> 32 whose first 64 input channels are shared: the shared part as ONE wide conv over an
     N-concatenated sub-block pack, the rest per conv with the pre-activation addend == the full convs."""
-    from crdr_amd.hip import functional as HF, lib as L, ops
+    from crdr_amd.hip import lib as L, ops, packs
     from crdr_amd.hip.ops import view
     n, h, w, hm, co = 1, 6, 8, 64, 32
     M = n * h * w
@@ -85,10 +85,10 @@ def test_sub_block_packs_and_hoisted_conv():
     X = wide(M, hm + max(extra))
     X.view(n, h, w, -1).copy_(x.permute(0, 2, 3, 1))
     hyp = torch.empty((9, 3 * co, hm), dtype=torch.float32, device=dev())
-    ents = [HF.sub_pack(ws[g], 0, hm, hyp, g * co * hm, co, hm, False, dld=hm, tstride=3 * co * hm) for g in range(3)]
+    ents = [packs.sub_pack(ws[g], 0, hm, hyp, g * co * hm, co, hm, False, dld=hm, tstride=3 * co * hm) for g in range(3)]
     sup = [torch.empty((9, co, e), dtype=torch.float32, device=dev()) for e in extra]
-    ents += [HF.sub_pack(ws[g], hm, hm + e, sup[g], 0, co, e, False) for g, e in enumerate(extra)]
-    HF.ensure_fresh(ents)
+    ents += [packs.sub_pack(ws[g], hm, hm + e, sup[g], 0, co, e, False) for g, e in enumerate(extra)]
+    packs.ensure_fresh(ents)
     A = wide(M, 3 * co)
     ops.conv_group(n, h, w, [view(X, 0, hm)], [hyp.data_ptr()], [view(A, 0, 3 * co)], 3 * co, (3, 3), 1, False, wrows=3 * co, wcols=hm,
                    device=dev())
@@ -112,7 +112,7 @@ def test_sub_block_packs_and_hoisted_conv():
 
         def numel(self):
             return (flat_hi - flat_lo) // 4
-    tb = HF.PackTable(_Flat())
+    tb = packs.PackTable(_Flat())
     tb.refill()
     mine = {id(e) for e in ents}
     assert mine <= {id(e) for e in tb.entries}

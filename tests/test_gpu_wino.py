@@ -359,11 +359,11 @@ def test_winograd_f4x4_split_k(case):
 
 
 def test_winograd_f4x4_persistent_filter_caches():
-    """ops' persistent filter caches: a second F(4x4) launch with the same registered weight pack reuses the transformed filters of the first
-    (same bits out), inside or outside a filter_scope; a pack rewritten in place is noticed through its version counter alone; temporary
-    packs are never cached; and the batched rebuild behind a pack refill (ops.FilterTable: one launch for every cache derived from a set of
+    """The persistent filter caches (hip/packs.py): a second F(4x4) launch with the same registered weight pack reuses the transformed filters of
+    the first (same bits out); a pack rewritten in place is noticed through its version counter alone; temporary
+    packs are never cached; and the batched rebuild behind a pack refill (packs.FilterTable: one launch for every cache derived from a set of
     packs) leaves exactly what the per-launch transform would have written, stamped current"""
-    from crdr_amd.hip import ops
+    from crdr_amd.hip import ops, packs
     dev = _dev()
     a4 = _wino_id() + 2
     x = _rand(2, 96, 16, 64, seed=1).to(dev)
@@ -375,18 +375,17 @@ def test_winograd_f4x4_persistent_filter_caches():
     call = lambda: ops.conv2d_raw(x, wp, 64, (3, 3), 1, 1, False, (16, 64), algo=a4)
     call5 = lambda: ops.conv2d_raw(x5, wp5, 96, (5, 5), 1, 2, False, (16, 16), algo=a4)
     ref1, ref5a = call(), call5()
-    st = ops.FILTER_SCOPE_STATS
+    st = packs.FILTER_STATS
     f0, r0 = st["filled"], st["reused"]
     assert torch.equal(call(), ref1) and (st["filled"], st["reused"]) == (f0, r0), "a temporary pack must not be cached by address"
-    ops.register_persistent_pack(wp)
-    ops.register_persistent_pack(wp5)
+    packs.register(wp)
+    packs.register(wp5)
     assert torch.equal(call(), ref1) and (st["filled"], st["reused"]) == (f0 + 1, r0)
-    with ops.filter_scope():
-        assert torch.equal(call(), ref1) and (st["filled"], st["reused"]) == (f0 + 1, r0 + 1)
+    assert torch.equal(call(), ref1) and (st["filled"], st["reused"]) == (f0 + 1, r0 + 1)
     assert torch.equal(call(), ref1) and (st["filled"], st["reused"]) == (f0 + 1, r0 + 2)
-    # a writer that only bumps the pack's version (what functional._PackEntry.fill / PackTable.refill do): the kept filters are NOT reused
+    # a writer that only bumps the pack's version (what packs._PackEntry.fill / PackTable.refill do): the kept filters are NOT reused
     wp.copy_(ops.pack_weight(w2, transpose=False))
-    ops.bump_pack_version(wp.data_ptr())
+    packs.bump_version(wp.data_ptr())
     out2 = call()
     assert (st["filled"], st["reused"]) == (f0 + 2, r0 + 2)
     assert torch.equal(call(), out2) and (st["filled"], st["reused"]) == (f0 + 2, r0 + 3)
@@ -396,9 +395,9 @@ def test_winograd_f4x4_persistent_filter_caches():
     assert torch.equal(call5(), ref5a)                                    # (creates the 5x5 cache)
     wp.copy_(ops.pack_weight(w1, transpose=False))
     wp5.copy_(ops.pack_weight(w5b, transpose=False))
-    ops.bump_pack_version(wp.data_ptr())
-    ops.bump_pack_version(wp5.data_ptr())
-    table = ops.FilterTable(dev)
+    packs.bump_version(wp.data_ptr())
+    packs.bump_version(wp5.data_ptr())
+    table = packs.FilterTable(dev)
     b0 = st["batched"]
     table.refill({wp.data_ptr(), wp5.data_ptr()})
     assert st["batched"] == b0 + 2 and len(table.entries) == 2
@@ -412,8 +411,8 @@ def test_winograd_f4x4_persistent_filter_caches():
     # a rebuild for OTHER packs leaves these caches alone; rebuilding again is idempotent
     table.refill({wp.data_ptr(), wp5.data_ptr()})
     assert torch.equal(call(), ref1) and torch.equal(call5(), fresh5)
-    ops.filter_scope_invalidate(wp.data_ptr())
-    ops.filter_scope_invalidate(wp5.data_ptr())
+    packs.drop_filter_caches(wp.data_ptr())
+    packs.drop_filter_caches(wp5.data_ptr())
 
 
 def test_winograd_f4x4_epilogues_slices_groups_colsum():

@@ -8,7 +8,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import bench  # noqa: E402
-from crdr_amd.hip import ops  # noqa: E402
+from crdr_amd.hip import ops, packs  # noqa: E402
 
 ops.AUTOTUNE = True
 ops.load_tune_cache(ops.DEFAULT_TUNE_DB)
@@ -19,10 +19,10 @@ for it in range(1, 7):
     tr.optimize_parameters(it, {**d, "rate_ind": it % 5})
 torch.cuda.synchronize()
 rows, per_pack = [], {}
-for key, e in ops._filter_cache.items():
-    wk, G = key[0], key[1]
-    rows.append({"G": G, "N": key[3], "H": key[4], "W": key[5], "C": key[6], "OC": key[9], "k": key[10], "stride": key[12], "transposed": key[14], "MB": round(e.nbytes / 1e6, 1),
-                 "packs": len(set(wk))})
+for key, e in packs._filter_cache.items():
+    wk = key.packs
+    rows.append({"G": key.G, "N": key.N, "H": key.H, "W": key.W, "C": key.C, "OC": key.OC, "k": key.kh, "stride": key.stride, "transposed": key.transposed,
+                 "MB": round(e.nbytes / 1e6, 1), "packs": len(set(wk))})
     for p in set(wk):
         per_pack.setdefault(p, []).append(e.nbytes / max(len(wk), 1))
 tot = sum(r["MB"] for r in rows)
