@@ -806,51 +806,105 @@ __global__ __launch_bounds__(kNT4) void wino4_kernel(const IgemmArgs p_, const I
 
 // Filter transform U = G g G^T, G = rows [1, p_j, p_j^2] / N_j at the points 0, +-a, +-b and [0, 0, 1] (wino4_xform.hpp), evaluated in double
 // and rounded once, from the implicit-GEMM weight pack (tap-major [tap][wrows][wcols]) into the block layout of wino4_kernel:
-// [N tile of 64][chunk of 4 channels][position 36][channel 4][oh 2][tx 16][ob 2], output channel = 32 oh + 16 ob + tx.
+// [N tile of 64][variant][chunk of 4 channels][position 36][channel 4][oh 2][tx 16][ob 2], output channel = 32 oh + 16 ob + tx.
 struct Wino4Taps { int widx[4][9]; };   // [variant][3 a + b]: weight-pack tap of sub-filter element (a, b), -1 = zero
-// one thread: (unit blk = (N tile, variant, chunk), oc, channel c of the chunk); variant = parity sub-filter of a stride-2 conv (blocks of one
-// tile: [sub][chunk] ... the K loop walks them) or output phase of a stride-2 transposed conv ([phase][chunk] as well, each phase being a
-// tile of its own); consecutive threads read consecutive input channels of one weight-pack row
-__device__ __forceinline__ void wino4_filter_thread(const float* w, float* ug, long long blk, int t256, int Cin, int Cout, int wrows, int wcols,
-                                                    int kchunks, int nvar, const int (&widx)[4][9]) {
-  const int c4 = t256 & 3, oc64 = (t256 >> 2) & 63;
-  const int kc = (int)(blk % kchunks), var = (int)((blk / kchunks) % nvar), ct = (int)(blk / ((long long)kchunks * nvar));
-  const int oc = ct * kBN4 + oc64, c = kc * 4 + c4;
-  const bool live = oc < Cout && c < Cin;
-  double g9[3][3];
+// one workgroup of 256 threads: a RUN of up to kRunChunks consecutive chunks of one (N tile, variant) -- 32 input channels = one 128-byte line
+// of every weight-pack row (wcols % 32 == 0); variant = parity sub-filter of a stride-2 conv (blocks of one tile: [sub][chunk] ... the K loop
+// walks them) or output phase of a stride-2 transposed conv ([phase][chunk] as well, each phase being a tile of its own).
+//   loads: 8 lanes x 16 bytes cover the line of one pack row, a wave load 8 whole lines; a thread keeps (row, chunk lane & 7) of both halves of
+//   the tile's 64 rows, nine taps each, in registers for the whole run.
+//   per chunk: the threads that hold it publish their taps through LDS ([tap][oc] of 16 bytes); thread (wave = channel of the chunk, lane =
+//   place of its output channel in [oh][tx][ob]) evaluates its 36 results into the chunk's block in LDS; the block leaves with 16 bytes per
+//   lane at consecutive addresses (1 KiB per wave store).  Chunks of a run are consecutive blocks of the cache: a run writes one span.
+constexpr int kRunChunks = 8;
+constexpr int kFilterBlocksPerCU = 3;   // 45 KiB of LDS and <= 168 registers: three workgroups per CU
+constexpr int wino4_filter_runs(int kchunks) { return (kchunks + kRunChunks - 1) / kRunChunks; }
+__device__ __forceinline__ void wino4_filter_block(const float* __restrict__ w, float* __restrict__ ug, long long unit, int Cin, int Cout, int wrows,
+                                                   int wcols, int kchunks, int nvar, const int (&widx)[4][9]) {
+  __shared__ float4 sU[kUSlots4];       // one chunk's block [position 36][channel 4][oh 2][tx 16][ob 2]
+  __shared__ float4 sG[9 * kBN4];       // the chunk's taps [tap][oc] x 4 channels
+  const int t256 = (int)threadIdx.x, lane = t256 & 63, wave = t256 >> 6;
+  const int nruns = wino4_filter_runs(kchunks);
+  const int run = (int)(unit % nruns), var = (int)((unit / nruns) % nvar), ct = (int)(unit / ((long long)nruns * nvar));
+  const int kc0 = run * kRunChunks, nch = min(kRunChunks, kchunks - kc0);
+  const bool vec = (wcols & 3) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0;   // (block-uniform; packs are built that way)
+  // ---- the run's taps: rows 32 h + 8 wave + lane / 8, channels 4 (kc0 + lane % 8) .. + 3
+  const int lrow = wave * 8 + (lane >> 3), lch = lane & 7, c0 = (kc0 + lch) * 4;
+  float4 gl[2][9];
 #pragma unroll
-  for (int a = 0; a < 3; ++a)
+  for (int h = 0; h < 2; ++h) {
+    const int oc = ct * kBN4 + h * 32 + lrow;
 #pragma unroll
-    for (int b = 0; b < 3; ++b) {
-      const int wi = widx[var][a * 3 + b];
-      g9[a][b] = (live && wi >= 0) ? (double)w[((size_t)wi * wrows + oc) * wcols + c] : 0.0;
+    for (int tp = 0; tp < 9; ++tp) {
+      const int wi = widx[var][tp];
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (oc < Cout && wi >= 0) {
+        const float* src = w + ((size_t)wi * wrows + oc) * wcols + c0;
+        if (vec && c0 + 3 < wcols) {
+          v = *reinterpret_cast<const float4*>(src);
+        } else {
+          if (c0 < Cin) v.x = src[0];
+          if (c0 + 1 < Cin) v.y = src[1];
+          if (c0 + 2 < Cin) v.z = src[2];
+          if (c0 + 3 < Cin) v.w = src[3];
+        }
+        if (c0 >= Cin) v.x = 0.f;
+        if (c0 + 1 >= Cin) v.y = 0.f;
+        if (c0 + 2 >= Cin) v.z = 0.f;
+        if (c0 + 3 >= Cin) v.w = 0.f;
+      }
+      gl[h][tp] = v;
     }
+  }
+  // ---- this thread's element of every chunk: channel `wave` of the chunk, output channel oc64 at float `lane` of the 64-float row
+  const int oc64 = (lane >> 5) * 32 + (lane & 1) * 16 + ((lane >> 1) & 15);
   const double wa = kWa, wb = kWb;
   const double G[6][3] = {{1.0 / kWN0, 0.0, 0.0}, {1.0 / kWNa, wa / kWNa, wa * wa / kWNa}, {1.0 / kWNa, -wa / kWNa, wa * wa / kWNa},
                           {1.0 / kWNb, wb / kWNb, wb * wb / kWNb}, {1.0 / kWNb, -wb / kWNb, wb * wb / kWNb}, {0.0, 0.0, 1.0}};
-  float* dst = ug + (size_t)blk * (kUSlots4 * 4) + (size_t)c4 * kBN4 + (oc64 >> 5) * 32 + (oc64 & 15) * 2 + ((oc64 >> 4) & 1);
+  float* sUf = reinterpret_cast<float*>(sU);
+  float4* dst = reinterpret_cast<float4*>(ug + ((size_t)(ct * nvar + var) * kchunks + kc0) * (kUSlots4 * 4));
+  for (int k = 0; k < nch; ++k) {
+    // (the barrier that ended the previous chunk's evaluation is behind every read of sG)
+    if (lch == k) {
 #pragma unroll
-  for (int xi = 0; xi < 6; ++xi) {
-    double t[3];
+      for (int h = 0; h < 2; ++h)
 #pragma unroll
-    for (int b = 0; b < 3; ++b) t[b] = G[xi][0] * g9[0][b] + G[xi][1] * g9[1][b] + G[xi][2] * g9[2][b];
+        for (int tp = 0; tp < 9; ++tp) sG[tp * kBN4 + h * 32 + lrow] = gl[h][tp];
+    }
+    __syncthreads();   // sG published; the previous chunk's block has left sU
+    double g9[3][3];
 #pragma unroll
-    for (int nu = 0; nu < 6; ++nu) dst[(size_t)(xi * 6 + nu) * 256] = (float)(G[nu][0] * t[0] + G[nu][1] * t[1] + G[nu][2] * t[2]);
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        const float4 v = sG[(a * 3 + b) * kBN4 + oc64];
+        g9[a][b] = (double)(wave == 0 ? v.x : wave == 1 ? v.y : wave == 2 ? v.z : v.w);
+      }
+#pragma unroll
+    for (int xi = 0; xi < 6; ++xi) {
+      double t[3];
+#pragma unroll
+      for (int b = 0; b < 3; ++b) t[b] = G[xi][0] * g9[0][b] + G[xi][1] * g9[1][b] + G[xi][2] * g9[2][b];
+#pragma unroll
+      for (int nu = 0; nu < 6; ++nu) sUf[(xi * 6 + nu) * 256 + t256] = (float)(G[nu][0] * t[0] + G[nu][1] * t[1] + G[nu][2] * t[2]);
+    }
+    __syncthreads();   // the block is complete; sG is free
+#pragma unroll
+    for (int i = 0; i < kUSlots4 / 256; ++i) dst[(size_t)k * kUSlots4 + i * 256 + t256] = sU[i * 256 + t256];
   }
+  // (a persistent caller's next unit: its first write of sG is behind the last barrier above, its first write of sU behind its own first barrier)
 }
-__global__ void wino4_filter_kernel(const IgemmGroup grp, int ngroup, const float* w0, float* u, int Cin, int Cout, int wrows, int wcols, int kchunks,
-                                    int ntile, int nvar, int var_inner, Wino4Taps tp) {
-  const long long total = (long long)ntile * nvar * kchunks * 256;
-  const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= total) return;
-  (void)var_inner;
+// the in-launch transform of a conv whose cache is not valid: one workgroup per unit, blockIdx.y = the group member
+__global__ __launch_bounds__(256, kFilterBlocksPerCU) void wino4_filter_kernel(const IgemmGroup grp, int ngroup, const float* w0, float* u, int Cin, int Cout,
+                                                                               int wrows, int wcols, int kchunks, int ntile, int nvar, Wino4Taps tp) {
   const int g = blockIdx.y;
   const float* w = ngroup > 1 ? grp.w[g] : w0;
-  wino4_filter_thread(w, u + (size_t)g * ntile * nvar * kchunks * (kUSlots4 * 4), id >> 8, (int)(id & 255), Cin, Cout, wrows, wcols, kchunks, nvar, tp.widx);
+  wino4_filter_block(w, u + (size_t)g * ntile * nvar * kchunks * (kUSlots4 * 4), blockIdx.x, Cin, Cout, wrows, wcols, kchunks, nvar, tp.widx);
 }
-// every filter cache of an optimiser in one launch (crdr_w4_filters_batched): a workgroup = one unit (256 threads) at a time, units dealt
-// round robin over a persistent grid; the item of a unit by binary search over the prefix table (block-uniform)
-__global__ __launch_bounds__(256) void wino4_filter_batched_kernel(const crdr_w4_filter_item* items, const long long* prefix, const long long* meta) {
+// every filter cache of an optimiser in one launch (crdr_w4_filters_batched): a workgroup = one unit at a time, units dealt round robin over a
+// persistent grid; the item of a unit by binary search over the prefix table (block-uniform)
+__global__ __launch_bounds__(256, kFilterBlocksPerCU) void wino4_filter_batched_kernel(const crdr_w4_filter_item* items, const long long* prefix,
+                                                                                       const long long* meta) {
   const int n = (int)meta[0];
   const long long total = meta[1];
   for (long long gu = blockIdx.x; gu < total; gu += gridDim.x) {
@@ -861,10 +915,10 @@ __global__ __launch_bounds__(256) void wino4_filter_batched_kernel(const crdr_w4
     }
     const crdr_w4_filter_item& it = items[lo];
     const long long ul = gu - prefix[lo];
-    const long long per = (long long)it.ntile * it.nvar * it.kchunks;   // units of one problem of the group
+    const long long per = (long long)it.ntile * it.nvar * wino4_filter_runs(it.kchunks);   // units of one problem of the group
     const int g = (int)(ul / per);
-    wino4_filter_thread(it.w[g], it.u + (size_t)g * per * (kUSlots4 * 4), ul - (long long)g * per, (int)threadIdx.x, it.Cin, it.Cout, it.wrows, it.wcols,
-                        it.kchunks, it.nvar, it.widx);
+    wino4_filter_block(it.w[g], it.u + (size_t)g * it.ntile * it.nvar * it.kchunks * (kUSlots4 * 4), ul - (long long)g * per, it.Cin, it.Cout, it.wrows,
+                       it.wcols, it.kchunks, it.nvar, it.widx);
   }
 }
 
@@ -1015,12 +1069,14 @@ int wino4_filter_item(const crdr_conv_desc* d, const IgemmTaps& taps, int G, crd
   it->kchunks = cdiv(d->C, 4); it->ntile = cdiv(d->OC, kBN4); it->nvar = mode >= 2 ? 4 : 1;
   for (int v = 0; v < 4; ++v)
     for (int t = 0; t < 9; ++t) it->widx[v][t] = wt.widx[v][t];
-  it->units = (long long)G * it->ntile * it->nvar * it->kchunks;
+  it->units = (long long)G * it->ntile * it->nvar * wino4_filter_runs(it->kchunks);   // work units of the batched rebuild: runs of 8 chunks
   return 0;
 }
 
 int wino4_filters_batched(const crdr_w4_filter_item* items, const long long* prefix, const long long* meta, hipStream_t s) {
-  hipLaunchKernelGGL(wino4_filter_batched_kernel, dim3(4096), dim3(256), 0, s, items, prefix, meta);
+  // the persistent grid: exactly the workgroups that are resident at once (units are 8x coarser than the single chunks the 4096-workgroup
+  // grid used to deal; grids of 3, 6 and 12 workgroups per CU measured the same time within 1.5 %)
+  hipLaunchKernelGGL(wino4_filter_batched_kernel, dim3(kFilterBlocksPerCU * cu_count()), dim3(256), 0, s, items, prefix, meta);
   CRDR_CHECK_LAUNCH("wino4_filter_batched_kernel");
   return 0;
 }
@@ -1036,9 +1092,8 @@ int wino4_launch(const crdr_conv_desc* d, IgemmArgs a, const IgemmTaps& taps, co
   const int nvar = mode >= 2 ? 4 : 1;
   const int ntile = cdiv(d->OC, kBN4), kchunks = cdiv(d->C, 4);
   if (!filters_ready) {   // (a caller that kept the transformed filters of these weights from an earlier launch skips this)
-    const long long total = (long long)ntile * nvar * kchunks * 256;
-    hipLaunchKernelGGL(wino4_filter_kernel, dim3((unsigned)cdiv64(total, 256), G), dim3(256), 0, s, grp, G, a.w, u, d->C, d->OC, d->wrows, d->wcols, kchunks,
-                       ntile, nvar, 0, wt);
+    hipLaunchKernelGGL(wino4_filter_kernel, dim3((unsigned)(ntile * nvar * wino4_filter_runs(kchunks)), G), dim3(256), 0, s, grp, G, a.w, u, d->C, d->OC,
+                       d->wrows, d->wcols, kchunks, ntile, nvar, wt);
     CRDR_CHECK_LAUNCH("wino4_filter_kernel");
   }
   a.w = u;
