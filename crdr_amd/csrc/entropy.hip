@@ -65,6 +65,8 @@ __device__ __forceinline__ float gc_lik(float a, float rs, float& e_lo, float& e
   const float l = 0.5f * ((xl < 0.f ? 2.f - tl : tl) - th);
   return a != a ? a : l;   // (the clamps above would swallow a NaN latent)
 }
+// max(l, bound) that keeps a NaN likelihood (fmaxf returns the bound): torch.max, which the reference's LowerBound is, propagates it
+__device__ __forceinline__ float gc_floor(float l, float bound) { return l < bound ? bound : l; }
 
 __device__ __forceinline__ float block_sum(float v, float* red) {  // any block size multiple of 64, <= 1024
 #pragma unroll
@@ -121,13 +123,13 @@ __device__ __forceinline__ void gc_elem(const GcArgs& p, float yv, float m, floa
   float e0, e1;
   if (want_q) {
     float l = gc_lik(fabsf(q), rs, e0, e1);  // |round(y - mu) + mu - mu|
-    l = fmaxf(l, p.d.likelihood_bound);
+    l = gc_floor(l, p.d.likelihood_bound);
     lq = l;
     sq -= __builtin_amdgcn_logf(l);   // v_log_f32 = log2 (l >= the bound: never denormal)
   }
   if (noisy) {
     float l = gc_lik(fabsf(yv + u - m), rs, e0, e1);
-    l = fmaxf(l, p.d.likelihood_bound);
+    l = gc_floor(l, p.d.likelihood_bound);
     ln = l;
     sn -= __builtin_amdgcn_logf(l);
   }
@@ -230,15 +232,15 @@ __device__ __forceinline__ void gc_elem_bwd(const GcArgs& p, float yv, float m, 
   const float zu = (0.5f - a) * inv_sg, zl = (-0.5f - a) * inv_sg;
   float e_lo, e_hi;
   const float lraw = gc_lik(a, rs, e_lo, e_hi);
-  const float l = fmaxf(lraw, p.d.likelihood_bound);
+  const float l = gc_floor(lraw, p.d.likelihood_bound);
   const float glik = gb * (-inv_ln2 / l);                                         // d(-log2 l)/dl scaled
-  const float graw = (lraw >= p.d.likelihood_bound || glik < 0.f) ? glik : 0.f;  // LowerBound backward
+  const float graw = (lraw < p.d.likelihood_bound && glik >= 0.f) ? 0.f : glik;  // LowerBound backward (a NaN passes, as in the forward)
   const float pu = 0.39894228040143267794f * e_lo, pl = 0.39894228040143267794f * e_hi;   // the densities at zu, zl
   const float dl_da = (pl - pu) * inv_sg;
   const float dl_dsg = (zl * pl - zu * pu) * inv_sg;
   const float gy = graw * dl_da * sgn;
   const float gsg = graw * dl_dsg;
-  gsig = (sraw >= p.d.scale_bound || gsg < 0.f) ? gsg : 0.f;
+  gsig = (sraw < p.d.scale_bound && gsg >= 0.f) ? 0.f : gsg;
   gy_out = gy + ste;   // yhat = ste_round(y - mu) + mu: d/dy = 1, d/dmu = 0
   gmu = -gy;
 }
@@ -602,7 +604,8 @@ __global__ __launch_bounds__(256) void gauss_symbols_kernel(const float* y, int 
                                                             int ldsg, const float* table, int levels, float bound, int N, int HW,
                                                             int C, int* sym, int* idx) {
   __shared__ float st[256];
-  for (int i = threadIdx.x; i < levels; i += 256) st[i] = table[i];
+  if (idx)   // a symbols-only call may leave the table NULL
+    for (int i = threadIdx.x; i < levels; i += 256) st[i] = table[i];
   __syncthreads();
   const long long total = (long long)N * C * HW;
   for (long long e = blockIdx.x * 256ll + threadIdx.x; e < total; e += gridDim.x * 256ll) {

@@ -441,12 +441,6 @@ def lrp(a, z):
     return _Lrp.apply(a, z)
 
 
-def _gc_desc(y, ldy, ldmu, ldsg, ldyh, scale_bound, lik_bound):
-    n, c, h, w = y.shape
-    return L.GcDesc(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldyhat=ldyh, scale_bound=scale_bound,
-                    likelihood_bound=lik_bound)
-
-
 def gauss_cond_fwd2(d, io, device) -> None:
     """crdr_gauss_cond_fwd2 with the scratch for its per-block partial bit sums attached (fixed-order finishing pass)."""
     lib = L.load()
@@ -470,11 +464,12 @@ class _GaussCond(torch.autograd.Function):
         bits_q = torch.zeros(n, dtype=torch.float32, device=dev)
         lik_n = ops.empty_nhwc(n, c, h, w, dev) if (want_lik and noise is not None) else None
         lik_q = ops.empty_nhwc(n, c, h, w, dev) if want_lik else None
+        ldn = 0
         if noise is not None:
             noise, ldn = ops.nhwc(noise)
-            if ldn != c:
-                noise = noise.contiguous(memory_format=torch.channels_last)
-        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldyhat=c, scale_bound=scale_bound, likelihood_bound=lik_bound)
+        ldo = ops.ld_for(c)   # the pixel stride of every buffer empty_nhwc made above
+        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldyhat=ldo, ldnoise=ldn, ldlik=ldo, scale_bound=scale_bound,
+                      likelihood_bound=lik_bound)
         io = L.GcIO(y=y.data_ptr(), mu=mu.data_ptr(), sigma=sigma.data_ptr(), noise=ops._p(noise), yhat=yhat.data_ptr(),
                     lik_noisy=ops._p(lik_n), lik_quant=ops._p(lik_q), bits_noisy=bits_n.data_ptr(), bits_quant=bits_q.data_ptr())
         gauss_cond_fwd2(d, io, dev)
@@ -503,11 +498,14 @@ class _GaussCond(torch.autograd.Function):
         lddyh = 0
         if dyhat is not None:
             dyhat, lddyh = ops.nhwc(dyhat)
+        noise, ldn = ops.nhwc(noise)
+        dbits_n = dbits_n.contiguous()
         dy, dmu, dsg = (ops.empty_nhwc(n, c, h, w, dev) for _ in range(3))
-        d = _gc_desc(y, ldy, ldmu, ldsg, c, *ctx.bounds)
-        L.check(lib.crdr_gauss_cond_bwd(C.byref(d), y.data_ptr(), mu.data_ptr(), sigma.data_ptr(), noise.data_ptr(),
-                                        dbits_n.contiguous().data_ptr(), ops._p(dyhat), lddyh, dy.data_ptr(),
-                                        dmu.data_ptr(), dsg.data_ptr(), ops._stream()), "gauss_cond_bwd")
+        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldnoise=ldn, ldgrad=ops.ld_for(c), lddyhat=lddyh,
+                      scale_bound=ctx.bounds[0], likelihood_bound=ctx.bounds[1])
+        io = L.GcIO(y=y.data_ptr(), mu=mu.data_ptr(), sigma=sigma.data_ptr(), noise=noise.data_ptr(), gbits=dbits_n.data_ptr(),
+                    dyhat=ops._p(dyhat), dy=dy.data_ptr(), dmu=dmu.data_ptr(), dsigma=dsg.data_ptr())
+        L.check(lib.crdr_gauss_cond_bwd2(C.byref(d), C.byref(io), ops._stream()), "gauss_cond_bwd2")
         return dy, dmu, dsg, None, None, None, None
 
 
@@ -531,7 +529,8 @@ class _GaussCondPhilox(torch.autograd.Function):
         bits_q = torch.zeros(n, dtype=torch.float32, device=dev)
         lik_n = ops.empty_nhwc(n, c, h, w, dev) if want_lik else None
         lik_q = ops.empty_nhwc(n, c, h, w, dev) if want_lik else None
-        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldyhat=c, Ctot=c, c0=0, scale_bound=scale_bound,
+        ldo = ops.ld_for(c)   # the pixel stride of every buffer empty_nhwc made above
+        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldyhat=ldo, ldlik=ldo, Ctot=c, c0=0, scale_bound=scale_bound,
                       likelihood_bound=lik_bound)
         io = L.GcIO(y=y.data_ptr(), mu=mu.data_ptr(), sigma=sigma.data_ptr(), philox=ph.data_ptr(), yhat=yhat.data_ptr(),
                     lik_noisy=ops._p(lik_n), lik_quant=ops._p(lik_q), bits_noisy=bits_n.data_ptr(), bits_quant=bits_q.data_ptr())
@@ -560,7 +559,7 @@ class _GaussCondPhilox(torch.autograd.Function):
         if dyhat is not None:
             dyhat, lddyh = ops.nhwc(dyhat)
         dy, dmu, dsg = (ops.empty_nhwc(n, c, h, w, dev) for _ in range(3))
-        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldgrad=c, lddyhat=lddyh, Ctot=c, c0=0,
+        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldgrad=ops.ld_for(c), lddyhat=lddyh, Ctot=c, c0=0,
                       scale_bound=ctx.bounds[0], likelihood_bound=ctx.bounds[1])
         io = L.GcIO(y=y.data_ptr(), mu=mu.data_ptr(), sigma=sigma.data_ptr(), philox=ph.data_ptr(), gbits=dbits_n.data_ptr(),
                     dyhat=ops._p(dyhat), dy=dy.data_ptr(), dmu=dmu.data_ptr(), dsigma=dsg.data_ptr())
@@ -576,22 +575,26 @@ def gauss_cond(y, mu, sigma, noise, scale_bound=0.11, lik_bound=1e-9, want_lik=F
     return _GaussCond.apply(y, mu, sigma, noise, float(scale_bound), float(lik_bound), bool(want_lik))
 
 
+def _dense_nhwc(t: torch.Tensor) -> torch.Tensor:
+    """A [N,C,H,W] tensor in NHWC memory whose pixel stride is C itself, for the kernels that take no stride."""
+    t, ld = ops.nhwc(t)
+    if ld != t.shape[1]:
+        t = t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    return t
+
+
 class _EntropyBottleneck(torch.autograd.Function):
     """(z, params[C,58], medians[C], noise) -> (z_hat, lik, bits[N])"""
 
     @staticmethod
     def forward(ctx, z, params, medians, noise, lik_bound):
         lib = L.load()
-        z, ldz = ops.nhwc(z)
+        z = _dense_nhwc(z)   # the kernels index element e of channel c at e * C + c: dense rows in, dense rows out
         n, c, h, w = z.shape
-        if ldz != c:
-            z = z.contiguous(memory_format=torch.channels_last)
         if noise is not None:
-            noise, ldn = ops.nhwc(noise)
-            if ldn != c:
-                noise = noise.contiguous(memory_format=torch.channels_last)
+            noise = _dense_nhwc(noise)
         dev = z.device
-        zhat, lik = ops.empty_nhwc(n, c, h, w, dev), ops.empty_nhwc(n, c, h, w, dev)
+        zhat, lik = ops.empty_nhwc(n, c, h, w, dev, ld=c), ops.empty_nhwc(n, c, h, w, dev, ld=c)
         bits = torch.zeros(n, dtype=torch.float32, device=dev)
         params = params.contiguous()
         medians = medians.contiguous()
@@ -614,10 +617,8 @@ class _EntropyBottleneck(torch.autograd.Function):
         if dbits is None:
             dbits = torch.zeros(n, dtype=torch.float32, device=dev)
         if dzhat is not None:
-            dzhat, ldd = ops.nhwc(dzhat)
-            if ldd != c:
-                dzhat = dzhat.contiguous(memory_format=torch.channels_last)
-        dz = ops.empty_nhwc(n, c, h, w, dev)
+            dzhat = _dense_nhwc(dzhat)
+        dz = ops.empty_nhwc(n, c, h, w, dev, ld=c)
         dparams = torch.empty_like(params)
         L.check(lib.crdr_entropy_bottleneck_bwd(z.data_ptr(), noise.data_ptr(), params.data_ptr(), n, h * w, c, ctx.lik_bound,
                                                 dbits.contiguous().data_ptr(), ops._p(dzhat), dz.data_ptr(),
