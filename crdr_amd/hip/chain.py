@@ -212,7 +212,7 @@ class _ChainFn(torch.autograd.Function):
             return [V(b.data_ptr(), cp, cc) for b in bufs], [_nchw(b, nn, hh, ww, cc) for b in bufs]
 
         def bias_slot(cv):
-            return HF._grad_slot(cv.bias) if (cv.bias is not None and cv.bias.requires_grad) else None
+            return HF.grad_slot(cv.bias) if (cv.bias is not None and cv.bias.requires_grad) else None
         try:
             # ---- gradient at the chain output(s).  An affine epilogue on the last conv (InterpChAtt) is undone by the
             # fused elementwise pass, which also yields d scale / d shift and the column sums of the pre-affine gradient.
@@ -274,7 +274,7 @@ class _ChainFn(torch.autograd.Function):
                     oh_, ow_ = dz_hw
                     wts = [cv.weight for cv in convs]
                     if wts[0].requires_grad:   # weight gradient: (dz, layer input)
-                        gp = [HF._grad_slot(wt).data_ptr() for wt in wts]
+                        gp = [HF.grad_slot(wt).data_ptr() for wt in wts]
                         if sp.transposed:
                             ops.wgrad_multi(n, ih, iw, oh_, ow_, lin, dz_v, gp, wts[0].shape[0], wts[0].shape[1], sp.k, sp.stride, sp.pad,
                                             device=dev, label=spec.name)

@@ -225,7 +225,7 @@ class CharmPlan:
 
     def bias_tables(self):
         """Device pointer tables for crdr_colsum_scatter: L1 / L2 biases in slot order, L3 biases in MSL order."""
-        g = HF._grad_slot
+        g = HF.grad_slot
         sig = (tuple(g(self.conv(k, i, 0).bias).data_ptr() for (k, i) in self.order),
                tuple(g(self.conv(k, i, 1).bias).data_ptr() for (k, i) in self.order),
                tuple(g(self.conv(k, i, 2).bias).data_ptr() for k in ("mean", "scale", "lrp") for i in range(self.S)))
@@ -462,7 +462,7 @@ def charm_backward(run: CharmRun, dyhat: Optional[torch.Tensor], gbits: Optional
     t1 = P.k1[0] * P.k1[1]
 
     def wg(kind, i, layer):
-        return HF._grad_slot(P.conv(kind, i, layer).weight)
+        return HF.grad_slot(P.conv(kind, i, layer).weight)
 
     def dgrad(xs, ws, ys, oc, k, wrows, wcols, masks=None, accum=False, label=""):
         for a, b in _chunks(len(xs)):

@@ -14,7 +14,7 @@ import torch
 from . import lib as L
 from . import ops, packs
 
-def _grad_slot(p: torch.Tensor) -> torch.Tensor:
+def grad_slot(p: torch.Tensor) -> torch.Tensor:
     if p.grad is None:
         p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
     return p.grad
@@ -132,7 +132,7 @@ class _FusedConv(torch.autograd.Function):
         if heavy or has_vec2:
             dz, gres, dgt, cs = ops.epilogue_bwd(dout, out, flags, vec2=vec2, scale=scale, shift=shift, gate_t=gt, sig=sig,
                                                  need_dz=bool(heavy),
-                                                 dbias_accum=_grad_slot(bias) if (has_bias and needs[2]) else None)
+                                                 dbias_accum=grad_slot(bias) if (has_bias and needs[2]) else None)
             if dz is None:
                 dz = dout
             if has_vec2:
@@ -142,7 +142,7 @@ class _FusedConv(torch.autograd.Function):
         else:
             dz = dout
             if has_bias and needs[2]:
-                ops.colsum(dz, _grad_slot(bias), accumulate=True)
+                ops.colsum(dz, grad_slot(bias), accumulate=True)
         if gres is None and (has_res or has_gate):
             gres = dout  # no affine in front: the residual branch sees dout itself
         dx = None
@@ -156,7 +156,7 @@ class _FusedConv(torch.autograd.Function):
         if needs[1]:
             # a parameter's gradient is accumulated straight into its (flat) slot; a derived weight (spectral norm) gets
             # its gradient returned through autograd instead, reduced immediately
-            g = torch.empty_like(weight) if ctx.return_wgrad else _grad_slot(weight)
+            g = torch.empty_like(weight) if ctx.return_wgrad else grad_slot(weight)
             g4 = g if g.dim() == 4 else g.view(g.shape[0], g.shape[1], 1, 1)
             kw = dict(accumulate=not ctx.return_wgrad, defer=not ctx.return_wgrad)
             if spec.transposed:
@@ -192,8 +192,8 @@ class _SmallLinear(torch.autograd.Function):
         dy2 = dy.reshape(m, o).contiguous()
         needs = ctx.needs_input_grad
         dx = torch.empty((m, i), dtype=torch.float32, device=dy.device) if needs[0] else None
-        dw = _grad_slot(weight) if needs[1] else None
-        db = _grad_slot(bias) if (bias is not None and needs[2]) else None
+        dw = grad_slot(weight) if needs[1] else None
+        db = grad_slot(bias) if (bias is not None and needs[2]) else None
         L.check(lib.crdr_linear_bwd(x2.data_ptr(), m, i, i, weight.data_ptr(), dy2.data_ptr(), o, None if y is None else y.data_ptr(),
                                     o, o, None if dx is None else dx.data_ptr(), i, None if dw is None else dw.data_ptr(),
                                     None if db is None else db.data_ptr(), ops._stream()), "linear_bwd")
@@ -245,8 +245,8 @@ class _LinearGroup(torch.autograd.Function):
             keep.append(dy)
             b = rest.pop(0) if ctx.has_b[k] else None
             g.w[k], g.dy[k], g.O[k] = ws[k].data_ptr(), dy.data_ptr(), o
-            g.dw[k] = _grad_slot(ws[k]).data_ptr() if needs[2 + k] else None
-            g.db[k] = _grad_slot(b).data_ptr() if (b is not None and needs[2 + n + k]) else None
+            g.dw[k] = grad_slot(ws[k]).data_ptr() if needs[2 + k] else None
+            g.db[k] = grad_slot(b).data_ptr() if (b is not None and needs[2 + n + k]) else None
         dx = torch.empty((m, i), dtype=torch.float32, device=x2.device) if needs[0] else None
         L.check(lib.crdr_linear_group_bwd(x2.data_ptr(), m, i, i, C.byref(g), n, None if dx is None else dx.data_ptr(), i,
                                           ops._stream()), "linear_group_bwd")
@@ -298,7 +298,7 @@ class _SpectralNorm(torch.autograd.Function):
         w_orig, u, v, sigma = ctx.saved_tensors
         lib = L.load()
         o, k = w_orig.shape[0], w_orig.numel() // w_orig.shape[0]
-        g = _grad_slot(w_orig)
+        g = grad_slot(w_orig)
         nb = lib.crdr_reduce_workspace(o * k) + 16
         ws, wsn = ops.workspace(nb, w_orig.device)
         L.check(lib.crdr_spectral_norm_bwd(dw_sn.contiguous().data_ptr(), w_orig.data_ptr(), u.data_ptr(), v.data_ptr(),
@@ -333,8 +333,8 @@ class _InterpCaVectors(torch.autograd.Function):
         # the bias gradients of the conv layers -- no zero-filled temporary, no autograd add per module
         direct = W.is_leaf and (ctx.B is None or ctx.B.is_leaf)
         if direct:
-            dW = _grad_slot(W) if ctx.needs_input_grad[0] else None
-            dB = _grad_slot(ctx.B) if (ctx.has_b and ctx.needs_input_grad[1]) else None
+            dW = grad_slot(W) if ctx.needs_input_grad[0] else None
+            dB = grad_slot(ctx.B) if (ctx.has_b and ctx.needs_input_grad[1]) else None
         else:
             dW = torch.zeros_like(W)
             dB = torch.zeros_like(W) if ctx.has_b else None
@@ -448,95 +448,53 @@ def gauss_cond_fwd2(d, io, device) -> None:
     L.check(lib.crdr_gauss_cond_fwd2(C.byref(d), C.byref(io), ops._stream()), "gauss_cond_fwd2")
 
 
+def _gc_operands(y, mu, sigma, noise, ph, bounds):
+    """What the forward and the backward of gauss_cond tell the kernels alike: the three operands as ops.nhwc hands them over with their
+    pixel strides, N / HW / C, the two bounds and the noise source -- the given samples with their pixel stride, or the (seed, offset) pair
+    `ph` the kernel draws them from (the tensor is the whole latent: Ctot = C, c0 = 0; with given samples the two stay at the library's
+    defaults).  -> (descriptor, io, (y, mu, sigma, noise) as passed); each direction adds its own fields."""
+    y, ldy = ops.nhwc(y)
+    mu, ldmu = ops.nhwc(mu)
+    sigma, ldsg = ops.nhwc(sigma)
+    n, c, h, w = y.shape
+    d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, scale_bound=bounds[0], likelihood_bound=bounds[1])
+    io = L.GcIO(y=y.data_ptr(), mu=mu.data_ptr(), sigma=sigma.data_ptr())
+    if ph is not None:
+        d.Ctot, d.c0, io.philox = c, 0, ph.data_ptr()
+    elif noise is not None:
+        noise, d.ldnoise = ops.nhwc(noise)
+        io.noise = noise.data_ptr()
+    return d, io, (y, mu, sigma, noise)
+
+
 class _GaussCond(torch.autograd.Function):
-    """(y, mu, sigma, noise) -> (y_hat, bits_noisy[N], bits_quant[N], lik_noisy?, lik_quant?)"""
+    """(y, mu, sigma, noise, philox_state) -> (y_hat, bits_noisy[N], bits_quant[N], lik_noisy?, lik_quant?).  `noise` given: those samples.
+    Else `philox_state`, the device (seed, offset) pair of the caller's generator, given: the noise is drawn in the kernel; the forward forks
+    its own pair off the state (crdr_philox_fork, so a captured graph draws fresh noise at every replay) and the backward regenerates the
+    same samples from that pair -- nothing is stored.  Neither: the quantised outputs only, and no backward."""
 
     @staticmethod
-    def forward(ctx, y, mu, sigma, noise, scale_bound, lik_bound, want_lik):
+    def forward(ctx, y, mu, sigma, noise, philox_state, scale_bound, lik_bound, want_lik):
         lib = L.load()
-        y, ldy = ops.nhwc(y)
-        mu, ldmu = ops.nhwc(mu)
-        sigma, ldsg = ops.nhwc(sigma)
-        n, c, h, w = y.shape
         dev = y.device
+        ph = None
+        if noise is None and philox_state is not None:
+            ph = torch.empty(2, dtype=torch.int64, device=dev)
+            L.check(lib.crdr_philox_fork(philox_state.data_ptr(), ph.data_ptr(), (y.numel() + 3) // 4 + 1, ops._stream()), "philox_fork")
+        d, io, (y, mu, sigma, noise) = _gc_operands(y, mu, sigma, noise, ph, (scale_bound, lik_bound))
+        n, c, h, w = y.shape
+        src = noise if ph is None else ph
         yhat = ops.empty_nhwc(n, c, h, w, dev)
         bits_n = torch.zeros(n, dtype=torch.float32, device=dev)
         bits_q = torch.zeros(n, dtype=torch.float32, device=dev)
-        lik_n = ops.empty_nhwc(n, c, h, w, dev) if (want_lik and noise is not None) else None
+        lik_n = ops.empty_nhwc(n, c, h, w, dev) if (want_lik and src is not None) else None
         lik_q = ops.empty_nhwc(n, c, h, w, dev) if want_lik else None
-        ldn = 0
-        if noise is not None:
-            noise, ldn = ops.nhwc(noise)
-        ldo = ops.ld_for(c)   # the pixel stride of every buffer empty_nhwc made above
-        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldyhat=ldo, ldnoise=ldn, ldlik=ldo, scale_bound=scale_bound,
-                      likelihood_bound=lik_bound)
-        io = L.GcIO(y=y.data_ptr(), mu=mu.data_ptr(), sigma=sigma.data_ptr(), noise=ops._p(noise), yhat=yhat.data_ptr(),
-                    lik_noisy=ops._p(lik_n), lik_quant=ops._p(lik_q), bits_noisy=bits_n.data_ptr(), bits_quant=bits_q.data_ptr())
+        d.ldyhat = d.ldlik = ops.ld_for(c)   # the pixel stride of every buffer empty_nhwc made above
+        io.yhat, io.lik_noisy, io.lik_quant = yhat.data_ptr(), ops._p(lik_n), ops._p(lik_q)
+        io.bits_noisy, io.bits_quant = bits_n.data_ptr(), bits_q.data_ptr()
         gauss_cond_fwd2(d, io, dev)
-        ctx.bounds = (scale_bound, lik_bound)
-        ctx.save_for_backward(y, mu, sigma, noise)
-        ctx.mark_non_differentiable(bits_q)
-        if lik_n is not None:
-            ctx.mark_non_differentiable(lik_n)
-        if lik_q is not None:
-            ctx.mark_non_differentiable(lik_q)
-        return yhat, bits_n, bits_q, lik_n, lik_q
-
-    @staticmethod
-    def backward(ctx, dyhat, dbits_n, _dq, _dln, _dlq):
-        y, mu, sigma, noise = ctx.saved_tensors
-        if noise is None:
-            raise L.CrdrHipError("gauss_cond: backward needs the noisy (training) forward")
-        lib = L.load()
-        y, ldy = ops.nhwc(y)
-        mu, ldmu = ops.nhwc(mu)
-        sigma, ldsg = ops.nhwc(sigma)
-        n, c, h, w = y.shape
-        dev = y.device
-        if dbits_n is None:
-            dbits_n = torch.zeros(n, dtype=torch.float32, device=dev)
-        lddyh = 0
-        if dyhat is not None:
-            dyhat, lddyh = ops.nhwc(dyhat)
-        noise, ldn = ops.nhwc(noise)
-        dbits_n = dbits_n.contiguous()
-        dy, dmu, dsg = (ops.empty_nhwc(n, c, h, w, dev) for _ in range(3))
-        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldnoise=ldn, ldgrad=ops.ld_for(c), lddyhat=lddyh,
-                      scale_bound=ctx.bounds[0], likelihood_bound=ctx.bounds[1])
-        io = L.GcIO(y=y.data_ptr(), mu=mu.data_ptr(), sigma=sigma.data_ptr(), noise=noise.data_ptr(), gbits=dbits_n.data_ptr(),
-                    dyhat=ops._p(dyhat), dy=dy.data_ptr(), dmu=dmu.data_ptr(), dsigma=dsg.data_ptr())
-        L.check(lib.crdr_gauss_cond_bwd2(C.byref(d), C.byref(io), ops._stream()), "gauss_cond_bwd2")
-        return dy, dmu, dsg, None, None, None, None
-
-
-class _GaussCondPhilox(torch.autograd.Function):
-    """_GaussCond with the noise drawn in the kernel: `philox_state` is the device (seed, offset) pair of the caller's generator; the
-    forward forks its own pair off it (crdr_philox_fork, so a captured graph draws fresh noise at every replay) and the backward
-    regenerates the same samples from that pair -- nothing is stored.  -> (y_hat, bits_noisy[N], bits_quant[N], lik_noisy?, lik_quant?)"""
-
-    @staticmethod
-    def forward(ctx, y, mu, sigma, philox_state, scale_bound, lik_bound, want_lik):
-        lib = L.load()
-        y, ldy = ops.nhwc(y)
-        mu, ldmu = ops.nhwc(mu)
-        sigma, ldsg = ops.nhwc(sigma)
-        n, c, h, w = y.shape
-        dev = y.device
-        ph = torch.empty(2, dtype=torch.int64, device=dev)
-        L.check(lib.crdr_philox_fork(philox_state.data_ptr(), ph.data_ptr(), (y.numel() + 3) // 4 + 1, ops._stream()), "philox_fork")
-        yhat = ops.empty_nhwc(n, c, h, w, dev)
-        bits_n = torch.zeros(n, dtype=torch.float32, device=dev)
-        bits_q = torch.zeros(n, dtype=torch.float32, device=dev)
-        lik_n = ops.empty_nhwc(n, c, h, w, dev) if want_lik else None
-        lik_q = ops.empty_nhwc(n, c, h, w, dev) if want_lik else None
-        ldo = ops.ld_for(c)   # the pixel stride of every buffer empty_nhwc made above
-        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldyhat=ldo, ldlik=ldo, Ctot=c, c0=0, scale_bound=scale_bound,
-                      likelihood_bound=lik_bound)
-        io = L.GcIO(y=y.data_ptr(), mu=mu.data_ptr(), sigma=sigma.data_ptr(), philox=ph.data_ptr(), yhat=yhat.data_ptr(),
-                    lik_noisy=ops._p(lik_n), lik_quant=ops._p(lik_q), bits_noisy=bits_n.data_ptr(), bits_quant=bits_q.data_ptr())
-        gauss_cond_fwd2(d, io, dev)
-        ctx.bounds = (scale_bound, lik_bound)
-        ctx.save_for_backward(y, mu, sigma, ph)
+        ctx.bounds, ctx.in_kernel = (scale_bound, lik_bound), ph is not None
+        ctx.save_for_backward(y, mu, sigma, src)   # the samples or the forked pair, never both
         ctx.mark_non_differentiable(bits_q)
         for t in (lik_n, lik_q):
             if t is not None:
@@ -545,42 +503,31 @@ class _GaussCondPhilox(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dyhat, dbits_n, _dq, _dln, _dlq):
-        y, mu, sigma, ph = ctx.saved_tensors
+        y, mu, sigma, src = ctx.saved_tensors
+        if src is None:
+            raise L.CrdrHipError("gauss_cond: backward needs the noisy (training) forward")
         lib = L.load()
-        y, ldy = ops.nhwc(y)
-        mu, ldmu = ops.nhwc(mu)
-        sigma, ldsg = ops.nhwc(sigma)
+        noise, ph = (None, src) if ctx.in_kernel else (src, None)
+        d, io, (y, mu, sigma, noise) = _gc_operands(y, mu, sigma, noise, ph, ctx.bounds)
         n, c, h, w = y.shape
         dev = y.device
         if dbits_n is None:
             dbits_n = torch.zeros(n, dtype=torch.float32, device=dev)
         dbits_n = dbits_n.contiguous()
-        lddyh = 0
         if dyhat is not None:
-            dyhat, lddyh = ops.nhwc(dyhat)
+            dyhat, d.lddyhat = ops.nhwc(dyhat)
         dy, dmu, dsg = (ops.empty_nhwc(n, c, h, w, dev) for _ in range(3))
-        d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=ldy, ldmu=ldmu, ldsigma=ldsg, ldgrad=ops.ld_for(c), lddyhat=lddyh, Ctot=c, c0=0,
-                      scale_bound=ctx.bounds[0], likelihood_bound=ctx.bounds[1])
-        io = L.GcIO(y=y.data_ptr(), mu=mu.data_ptr(), sigma=sigma.data_ptr(), philox=ph.data_ptr(), gbits=dbits_n.data_ptr(),
-                    dyhat=ops._p(dyhat), dy=dy.data_ptr(), dmu=dmu.data_ptr(), dsigma=dsg.data_ptr())
+        d.ldgrad = ops.ld_for(c)
+        io.gbits, io.dyhat = dbits_n.data_ptr(), ops._p(dyhat)
+        io.dy, io.dmu, io.dsigma = dy.data_ptr(), dmu.data_ptr(), dsg.data_ptr()
         L.check(lib.crdr_gauss_cond_bwd2(C.byref(d), C.byref(io), ops._stream()), "gauss_cond_bwd2")
-        return dy, dmu, dsg, None, None, None, None
+        return dy, dmu, dsg, None, None, None, None, None
 
 
 def gauss_cond(y, mu, sigma, noise, scale_bound=0.11, lik_bound=1e-9, want_lik=False, philox_state=None):
     """noise given: those samples; noise None and `philox_state` (device int64 [seed, offset]) given: in-kernel Philox noise; both
     None: the quantised (eval) outputs only."""
-    if noise is None and philox_state is not None:
-        return _GaussCondPhilox.apply(y, mu, sigma, philox_state, float(scale_bound), float(lik_bound), bool(want_lik))
-    return _GaussCond.apply(y, mu, sigma, noise, float(scale_bound), float(lik_bound), bool(want_lik))
-
-
-def _dense_nhwc(t: torch.Tensor) -> torch.Tensor:
-    """A [N,C,H,W] tensor in NHWC memory whose pixel stride is C itself, for the kernels that take no stride."""
-    t, ld = ops.nhwc(t)
-    if ld != t.shape[1]:
-        t = t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    return t
+    return _GaussCond.apply(y, mu, sigma, noise, philox_state, float(scale_bound), float(lik_bound), bool(want_lik))
 
 
 class _EntropyBottleneck(torch.autograd.Function):
@@ -589,10 +536,10 @@ class _EntropyBottleneck(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, params, medians, noise, lik_bound):
         lib = L.load()
-        z = _dense_nhwc(z)   # the kernels index element e of channel c at e * C + c: dense rows in, dense rows out
+        z = ops.dense_nhwc(z)   # the kernels index element e of channel c at e * C + c: dense rows in, dense rows out
         n, c, h, w = z.shape
         if noise is not None:
-            noise = _dense_nhwc(noise)
+            noise = ops.dense_nhwc(noise)
         dev = z.device
         zhat, lik = ops.empty_nhwc(n, c, h, w, dev, ld=c), ops.empty_nhwc(n, c, h, w, dev, ld=c)
         bits = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -617,7 +564,7 @@ class _EntropyBottleneck(torch.autograd.Function):
         if dbits is None:
             dbits = torch.zeros(n, dtype=torch.float32, device=dev)
         if dzhat is not None:
-            dzhat = _dense_nhwc(dzhat)
+            dzhat = ops.dense_nhwc(dzhat)
         dz = ops.empty_nhwc(n, c, h, w, dev, ld=c)
         dparams = torch.empty_like(params)
         L.check(lib.crdr_entropy_bottleneck_bwd(z.data_ptr(), noise.data_ptr(), params.data_ptr(), n, h * w, c, ctx.lik_bound,
@@ -679,15 +626,28 @@ def _unflat(flat, shape, geom):
     return flat.view(n, h, w, ld).permute(0, 3, 1, 2)[:, :c]
 
 
-class _SqDiffSum(torch.autograd.Function):
+# public name -> (sum entry, backward entry, takes a target) of the crdr_* ABI
+_PAIR_SUMS = {"sqdiff_sum": ("sqdiff_sum", "sqdiff_bwd", False),
+              "l1_sum": ("l1_sum", "l1_bwd", False),           # sum |a - b| (nn.L1Loss before its mean); gradient sign(a - b), sign(0) = 0
+              "bce_diff_sum": ("bce_diff_sum", "bce_diff_bwd", True)}   # sum BCEWithLogits(a - b, target)
+
+
+class _PairSum(torch.autograd.Function):
+    """(a, b) -> one float: a sum over the elements of a pair, by the _PAIR_SUMS entry `name`."""
+
     @staticmethod
-    def forward(ctx, a, b):
+    def forward(ctx, a, b, name, target):
         lib = L.load()
-        fa, fb, ctx.geom = _same_layout(a, b)
+        entry, _, has_target = _PAIR_SUMS[name]
+        if has_target:   # (the older rule: each operand flattened in its own contiguous order)
+            fa, fb, ctx.geom = a.contiguous().reshape(-1), b.contiguous().reshape(-1), None
+        else:
+            fa, fb, ctx.geom = _same_layout(a, b)
+        ctx.name, ctx.targs = name, ((target,) if has_target else ())
         out = torch.empty(1, dtype=torch.float32, device=a.device)
-        nb = lib.crdr_reduce_workspace(fa.numel())
-        ws, wsn = ops.workspace(nb, a.device)
-        L.check(lib.crdr_sqdiff_sum(fa.data_ptr(), fb.data_ptr(), fa.numel(), out.data_ptr(), ws, wsn, ops._stream()), "sqdiff_sum")
+        ws, wsn = ops.workspace(lib.crdr_reduce_workspace(fa.numel()), a.device)
+        L.check(getattr(lib, "crdr_" + entry)(fa.data_ptr(), fb.data_ptr(), fa.numel(), *ctx.targs, out.data_ptr(), ws, wsn, ops._stream()),
+                entry)
         ctx.shapes = (a.shape, b.shape)
         ctx.save_for_backward(fa, fb)   # (views of a, b wherever those already had the common layout)
         return out
@@ -696,86 +656,32 @@ class _SqDiffSum(torch.autograd.Function):
     def backward(ctx, g):
         fa, fb = ctx.saved_tensors
         lib = L.load()
+        entry = _PAIR_SUMS[ctx.name][1]
         da = torch.empty_like(fa) if ctx.needs_input_grad[0] else None
         db = torch.empty_like(fb) if ctx.needs_input_grad[1] else None
-        L.check(lib.crdr_sqdiff_bwd(fa.data_ptr(), fb.data_ptr(), fa.numel(), g.contiguous().data_ptr(), 1.0, ops._p(da),
-                                    ops._p(db), ops._stream()), "sqdiff_bwd")
-        return _unflat(da, ctx.shapes[0], ctx.geom), _unflat(db, ctx.shapes[1], ctx.geom)
+        L.check(getattr(lib, "crdr_" + entry)(fa.data_ptr(), fb.data_ptr(), fa.numel(), *ctx.targs, g.contiguous().data_ptr(), 1.0,
+                                              ops._p(da), ops._p(db), ops._stream()), entry)
+        return _unflat(da, ctx.shapes[0], ctx.geom), _unflat(db, ctx.shapes[1], ctx.geom), None, None
 
 
 def sqdiff_sum(a, b):
-    return _SqDiffSum.apply(a, b)
-
-
-class _L1Sum(torch.autograd.Function):
-    """sum |a - b| (nn.L1Loss before its mean); gradient sign(a - b), sign(0) = 0"""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        lib = L.load()
-        fa, fb, ctx.geom = _same_layout(a, b)
-        out = torch.empty(1, dtype=torch.float32, device=a.device)
-        ws, wsn = ops.workspace(lib.crdr_reduce_workspace(fa.numel()), a.device)
-        L.check(lib.crdr_l1_sum(fa.data_ptr(), fb.data_ptr(), fa.numel(), out.data_ptr(), ws, wsn, ops._stream()), "l1_sum")
-        ctx.shapes = (a.shape, b.shape)
-        ctx.save_for_backward(fa, fb)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        fa, fb = ctx.saved_tensors
-        lib = L.load()
-        da = torch.empty_like(fa) if ctx.needs_input_grad[0] else None
-        db = torch.empty_like(fb) if ctx.needs_input_grad[1] else None
-        L.check(lib.crdr_l1_bwd(fa.data_ptr(), fb.data_ptr(), fa.numel(), g.contiguous().data_ptr(), 1.0, ops._p(da), ops._p(db),
-                                ops._stream()), "l1_bwd")
-        return _unflat(da, ctx.shapes[0], ctx.geom), _unflat(db, ctx.shapes[1], ctx.geom)
+    return _PairSum.apply(a, b, "sqdiff_sum", None)
 
 
 def l1_sum(a, b):
-    return _L1Sum.apply(a, b)
-
-
-class _BceDiffSum(torch.autograd.Function):
-    """sum BCEWithLogits(p - q, target)"""
-
-    @staticmethod
-    def forward(ctx, p, q, target):
-        lib = L.load()
-        fp, fq = p.contiguous().reshape(-1), q.contiguous().reshape(-1)
-        out = torch.empty(1, dtype=torch.float32, device=p.device)
-        nb = lib.crdr_reduce_workspace(fp.numel())
-        ws, wsn = ops.workspace(nb, p.device)
-        L.check(lib.crdr_bce_diff_sum(fp.data_ptr(), fq.data_ptr(), fp.numel(), float(target), out.data_ptr(), ws, wsn,
-                                      ops._stream()), "bce_diff_sum")
-        ctx.target = float(target)
-        ctx.save_for_backward(fp, fq)
-        ctx.shape = p.shape
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        fp, fq = ctx.saved_tensors
-        lib = L.load()
-        dp = torch.empty_like(fp) if ctx.needs_input_grad[0] else None
-        dq = torch.empty_like(fq) if ctx.needs_input_grad[1] else None
-        L.check(lib.crdr_bce_diff_bwd(fp.data_ptr(), fq.data_ptr(), fp.numel(), ctx.target, g.contiguous().data_ptr(), 1.0,
-                                      ops._p(dp), ops._p(dq), ops._stream()), "bce_diff_bwd")
-        return (None if dp is None else dp.view(ctx.shape)), (None if dq is None else dq.view(ctx.shape)), None
+    return _PairSum.apply(a, b, "l1_sum", None)
 
 
 def bce_diff_sum(p, q, target: float):
-    return _BceDiffSum.apply(p, q, float(target))
+    return _PairSum.apply(p, q, "bce_diff_sum", float(target))
 
 
 class _MaxPool3s2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         lib = L.load()
-        x, ld = ops.nhwc(x)
+        x = ops.dense_nhwc(x)
         n, c, h, w = x.shape
-        if ld != c:
-            x = x.contiguous(memory_format=torch.channels_last)
         oh, ow = (h - 3) // 2 + 1, (w - 3) // 2 + 1
         y = ops.empty_nhwc(n, c, oh, ow, x.device, ld=c)   # the kernel takes no stride: dense rows in, dense rows out
         L.check(lib.crdr_maxpool3s2_fwd(x.data_ptr(), y.data_ptr(), n, h, w, c, ops._stream()), "maxpool_fwd")
@@ -787,9 +693,7 @@ class _MaxPool3s2(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         lib = L.load()
         n, c, h, w = x.shape
-        dy, ld = ops.nhwc(dy)
-        if ld != c:
-            dy = dy.contiguous(memory_format=torch.channels_last)
+        dy = ops.dense_nhwc(dy)
         dx = ops.empty_nhwc(n, c, h, w, x.device, ld=c)
         L.check(lib.crdr_maxpool3s2_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), n, h, w, c, ops._stream()), "maxpool_bwd")
         return dx
@@ -805,13 +709,8 @@ class _LpipsLayer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, f0, f1, lin):
         lib = L.load()
-        f0, l0 = ops.nhwc(f0)
-        f1, l1 = ops.nhwc(f1)
+        f0, f1 = ops.dense_nhwc(f0), ops.dense_nhwc(f1)
         n, c, h, w = f0.shape
-        if l0 != c:
-            f0 = f0.contiguous(memory_format=torch.channels_last)
-        if l1 != c:
-            f1 = f1.contiguous(memory_format=torch.channels_last)
         out = torch.zeros(n, dtype=torch.float32, device=f0.device)
         ws, wsn = ops.workspace(n * 64 * 4, f0.device)
         L.check(lib.crdr_lpips_layer_fwd(f0.data_ptr(), f1.data_ptr(), lin.data_ptr(), n, h * w, c, out.data_ptr(), ws, wsn,

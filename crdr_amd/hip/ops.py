@@ -393,12 +393,19 @@ def reserve_workspace(device, stream: "torch.cuda.Stream") -> None:
         _ws_cache[key] = torch.zeros(need, dtype=torch.uint8, device=dev)
 
 
+def _pixel_stride(t: torch.Tensor) -> int:
+    """Distance in elements between two pixels of a [N,C,H,W] tensor in NHWC memory, read off the first dimension that has more than one
+    entry; a single pixel has no neighbour and counts as dense (C)."""
+    n, c, h, w = t.shape
+    return t.stride(3) if w > 1 else (t.stride(2) if h > 1 else (t.stride(0) if n > 1 else c))
+
+
 def nhwc(t: torch.Tensor) -> Tuple[torch.Tensor, int]:
     """Return (tensor, pixel stride) for a [N,C,H,W] tensor whose memory is NHWC (possibly a channel slice);
     copies into channels_last if the layout is anything else."""
     _require_gpu(t)
     n, c, h, w = t.shape
-    ld = t.stride(3) if w > 1 else (t.stride(2) if h > 1 else (t.stride(0) if n > 1 else c))
+    ld = _pixel_stride(t)
     ok = (c == 1 or t.stride(1) == 1) and ld >= c
     ok = ok and (w == 1 or t.stride(3) == ld) and (h == 1 or t.stride(2) == w * ld) and (n == 1 or t.stride(0) == h * w * ld)
     if not ok or ld % 4 != 0 or (t.data_ptr() % 16) != 0:
@@ -414,6 +421,20 @@ def nhwc(t: torch.Tensor) -> Tuple[torch.Tensor, int]:
             t = buf.permute(0, 3, 1, 2)[:, :c]
             ld = cp
     return t, ld
+
+
+def dense_nhwc(t: torch.Tensor) -> torch.Tensor:
+    """A [N,C,H,W] tensor in NHWC memory whose pixel stride is C itself: the operand of a kernel that takes no stride.  Copies only when
+    nhwc() gives another stride (a channel slice of a wider buffer, padded image lanes), through permute / contiguous / permute, which
+    yields real NHWC memory at every size.  x.contiguous(memory_format=torch.channels_last) under the same condition, which some call
+    sites used to spell out, gives the same elements in the same order and copies in the same cases: torch skips the copy only where
+    every dimension with more than one entry already has its dense NHWC stride, and then nhwc() reports C.  The one tensor whose strides
+    torch does not look at at all is a single pixel (N = H = W = 1); nhwc() takes its stride as C, so neither form copies it.  (nhwc() pads
+    C % 4 != 0 to four-lane pixels whatever comes in, so such a tensor is copied even when it is dense already.)"""
+    t, ld = nhwc(t)
+    if ld != t.shape[1]:
+        t = t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    return t
 
 
 def ld_for(c: int) -> int:
@@ -615,7 +636,7 @@ def conv2d_raw(x: torch.Tensor, wpack: torch.Tensor, oc: int, k: Tuple[int, int]
     oh, ow = out_hw
     if out is None:
         out = empty_nhwc(n, oc, oh, ow, x.device)
-    out_t, ldy = out, (out.stride(3) if ow > 1 else (out.stride(2) if oh > 1 else (out.stride(0) if n > 1 else oc)))
+    out_t, ldy = out, _pixel_stride(out)
     d = L.ConvDesc(N=n, H=h, W=w, C=(c + 3) // 4 * 4 if ldx >= (c + 3) // 4 * 4 else c, OH=oh, OW=ow, OC=oc, kh=k[0], kw=k[1],
                    stride=stride, pad=pad, transposed=int(transposed), ldx=ldx, ldy=ldy, wrows=wpack.shape[1],
                    wcols=wpack.shape[2], flags=flags, ldres=0, ldg=0, wlayout=wlayout, reserved=0)
@@ -629,8 +650,7 @@ def conv2d_raw(x: torch.Tensor, wpack: torch.Tensor, oc: int, k: Tuple[int, int]
         gate_x, ldg = nhwc(gate_x)
         gate_t, ldg2 = nhwc(gate_t)
         if ldg != ldg2 or ldg != oc:
-            gate_x = gate_x.contiguous(memory_format=torch.channels_last)
-            gate_t = gate_t.contiguous(memory_format=torch.channels_last)
+            gate_x, gate_t = dense_nhwc(gate_x), dense_nhwc(gate_t)
             ldg = oc
         d.ldg = ldg
         io.gx, io.gt, io.sig = gate_x.data_ptr(), gate_t.data_ptr(), sig_out.data_ptr()

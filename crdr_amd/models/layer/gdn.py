@@ -48,7 +48,7 @@ class _GdnFn(torch.autograd.Function):
         nb = lib.crdr_gdn_workspace(C.byref(d), 1)
         ws = torch.empty(nb + 256, dtype=torch.uint8, device=x.device)
         p = (ws.data_ptr() + 255) // 256 * 256
-        gb, gg = HF._grad_slot(beta), HF._grad_slot(gamma)
+        gb, gg = HF.grad_slot(beta), HF.grad_slot(gamma)
         L.check(lib.crdr_gdn_bwd(C.byref(d), x.data_ptr(), beta.data_ptr(), gamma.data_ptr(), dy.data_ptr(), lddy, dx.data_ptr(),
                                  ops.ld_for(c), gb.data_ptr(), gg.data_ptr(), p, nb, ops._stream()), "gdn_bwd")
         return dx, None, None, None, None, None

@@ -78,8 +78,8 @@ class _ChannelNormFn(torch.autograd.Function):
         x, gamma, beta, stats = ctx.saved_tensors
         ldx, eps, act, slope, has_res = ctx.cfg
         needs = ctx.needs_input_grad
-        gg = HF._grad_slot(gamma) if (gamma is not None and needs[1]) else None
-        gb = HF._grad_slot(beta) if (beta is not None and needs[2]) else None
+        gg = HF.grad_slot(gamma) if (gamma is not None and needs[1]) else None
+        gb = HF.grad_slot(beta) if (beta is not None and needs[2]) else None
         dx = channel_norm_bwd(x, ldx, gamma, beta, stats, dy, eps=eps, act=act, slope=slope, dgamma=gg, dbeta=gb)
         return dx, None, None, (dy if has_res else None), None, None, None
 

@@ -1,7 +1,7 @@
 """Direct GPU parity of the loss, LPIPS and spectral-norm ops of csrc/eltwise.hip, each through its crdr_amd.hip.functional wrapper (or
 the module that owns its buffers), against the float64 restatements of tests/eltwise_ref.py and the oracle's spectral norm /
 interpolated channel-attention vectors: lrp, maxpool3s2, lpips_layer, sqdiff_sum, l1_sum, bce_diff_sum (values and gradients),
-spectral_norm_weight and interp_ca_vectors.
+spectral_norm_weight and interp_ca_vectors; ops.dense_nhwc, which hands the kernels without a stride argument their operands.
 
 Gates: elementwise outputs and input gradients within 2e-5 of the reference tensor's largest magnitude, parameter gradients within 5e-5
 (the gates tests/test_gpu_hific.py holds GDN and ChannelNorm to); max-pool values, gradient positions on integer data and every
@@ -58,6 +58,91 @@ def exact(what, got, ref):
     n = int((got.double() != ref.double()).sum())
     print(f"{what}: {n} of {ref.numel()} elements differ (gate 0)")
     assert n == 0, (what, n)
+
+
+# ---- ops.dense_nhwc ----------------------------------------------------------------------------------------------------------------------
+
+def _wide_of(t, ctot, c0):
+    """a ctot-wide dense NHWC device tensor that holds `t` (CPU, NCHW) in its channels [c0, c0 + C) and 77 in the others"""
+    n, c, h, w = t.shape
+    wide = torch.full((n, h, w, ctot), 77.0, device=dev()).permute(0, 3, 1, 2)
+    wide[:, c0:c0 + c] = t.to(dev())
+    return wide.detach()
+
+
+def _slice_of(t, ctot, c0):
+    return _wide_of(t, ctot, c0)[:, c0:c0 + t.shape[1]]
+
+
+DENSE_CASES = {"slice_w5": ((2, 8, 1, 5), lambda t: _slice_of(t, 16, 4), True),
+               "nchw_w1": ((1, 6, 3, 1), lambda t: t.to(dev()).contiguous(), True),
+               "pixels_of_8": ((3, 4, 1, 1), lambda t: _slice_of(t, 8, 4), True),
+               "one_pixel_of_16": ((1, 8, 1, 1), lambda t: _slice_of(t, 16, 4), False)}
+
+
+@pytest.mark.parametrize("name", list(DENSE_CASES))
+def test_dense_nhwc_is_the_input_in_dense_nhwc_memory(name):
+    """ops.dense_nhwc on the shapes where x.contiguous(memory_format=torch.channels_last), which some wrappers used instead, leaves strides
+    of one-entry dimensions to torch: the result equals the input, its memory read in N, H, W, C order at pixel stride C reproduces it, and
+    it is a copy exactly where ops.nhwc reports a pixel stride other than C.  A single pixel has no pixel stride: it is dense as it is.
+    The result itself is dense: where ops.nhwc takes it in place (C % 4 == 0; it pads any other C to four-lane pixels first) a second call
+    hands it back."""
+    from crdr_amd.hip import ops
+    shape, put, copies = DENSE_CASES[name]
+    n, c, h, w = shape
+    x = put(seeded_input(f"elt.dense.{name}", shape))
+    assert (ops.nhwc(x)[1] != c) == copies, name
+    r = ops.dense_nhwc(x)
+    exact(f"dense_nhwc {name} values", r, x)
+    rows = torch.as_strided(r, (n, h, w, c), (h * w * c, w * c, c, 1), r.storage_offset())
+    exact(f"dense_nhwc {name} memory in N,H,W,C order at stride C", rows, x.permute(0, 2, 3, 1))
+    assert (r.data_ptr() != x.data_ptr()) == copies, name
+    again = ops.dense_nhwc(r)
+    exact(f"dense_nhwc {name} applied twice", again, x)
+    assert c % 4 != 0 or again.data_ptr() == r.data_ptr(), name + ": a dense tensor was copied"
+
+
+def test_dense_nhwc_returns_a_dense_tensor_itself():
+    from crdr_amd.hip import ops
+    x = cl(seeded_input("elt.dense.cl", (2, 8, 3, 5)))
+    r = ops.dense_nhwc(x)
+    assert r.data_ptr() == x.data_ptr() and r.stride() == x.stride()
+
+
+@pytest.mark.parametrize("h,w", [(7, 7), (3, 3)])
+def test_maxpool_channel_slice_equals_dense_copy(h, w):
+    """Input and cotangent as channels [4, 12) of 16-wide NHWC buffers against the same call on dense clones: bit-equal forward and
+    gradient.  The kernel refuses W < 3 (a W = 1 input has no window), so 3x3, the smallest size it accepts, stands for the narrow case."""
+    oh, ow = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+    x = R.pool_input(8, h, w)
+    cot = seeded_input(f"elt.pool.slice.cot{h}x{w}", (2, 8, oh, ow))
+    wide = _wide_of(x, 16, 4).requires_grad_(True)
+    dense = cl(x).requires_grad_(True)
+    y = HF().maxpool3s2(wide[:, 4:12])
+    y.backward(_slice_of(cot, 16, 4))
+    y0 = HF().maxpool3s2(dense)
+    y0.backward(cl(cot))
+    assert torch.equal(y, y0), "forward"
+    assert torch.equal(wide.grad[:, 4:12], dense.grad), "gradient"
+    assert not bool(wide.grad[:, :4].any()) and not bool(wide.grad[:, 12:].any()), "gradient outside the slice"
+    exact(f"maxpool slice {h}x{w} y against float64", y, R.maxpool3s2(x.double()))
+
+
+@pytest.mark.parametrize("h,w", [(7, 7), (7, 1)])
+def test_lpips_layer_channel_slices_equal_dense_copies(h, w):
+    """both feature maps as channels [4, 12) of 16-wide NHWC buffers against the same call on dense clones: bit-equal value and gradient"""
+    f0, f1, lin, g = R.lpips_inputs(2, 8, h, w)
+    wide = _wide_of(f1, 16, 4).requires_grad_(True)
+    dense = cl(f1).requires_grad_(True)
+    lind, gd = lin.to(dev()), g.to(dev())
+    v = HF().lpips_layer(_slice_of(f0, 16, 4), wide[:, 4:12], lind)
+    v.backward(gd)
+    v0 = HF().lpips_layer(cl(f0), dense, lind)
+    v0.backward(gd)
+    assert torch.equal(v, v0), "value"
+    assert torch.equal(wide.grad[:, 4:12], dense.grad), "gradient"
+    assert not bool(wide.grad[:, :4].any()) and not bool(wide.grad[:, 12:].any()), "gradient outside the slice"
+    gate(f"lpips slice {h}x{w} value against float64", v, R.lpips_layer(f0.double(), f1.double(), lin.double()), 2e-5)
 
 
 # ---- lrp ---------------------------------------------------------------------------------------------------------------------------------
@@ -294,6 +379,27 @@ def test_reduction_matches_float64(name, n, shape4):
                 mags = g.reshape(-1).abs().cpu()
                 nz = mags[mags != 0]
                 exact(f"{what} {side} magnitudes", nz, torch.full_like(nz, float(torch.tensor(0.37))))
+
+
+@pytest.mark.parametrize("grad_to", [0, 1])
+@pytest.mark.parametrize("name", ["sqdiff", "l1", "bce0.9"])
+def test_reduction_allocates_only_the_gradient_that_is_needed(name, grad_to):
+    """requires_grad on one operand of n = 4096: the other side's gradient is None and no buffer is made for it -- the backward leaves
+    exactly one 16 KiB gradient behind, and at its peak holds less than two (the gradient, the one-element upstream gradient)"""
+    n = 4096
+    hip, _, (a, b), _ = _reduce_case(name, n)
+    opsd = [a.to(dev()), b.to(dev())]
+    opsd[grad_to].requires_grad_(True)
+    v = hip(*opsd)
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    m0 = torch.cuda.memory_allocated()
+    v.backward()
+    torch.cuda.synchronize()
+    kept, peak = torch.cuda.memory_allocated() - m0, torch.cuda.max_memory_allocated() - m0
+    print(f"{name} n={n} grad to {'ab'[grad_to]}: backward keeps {kept} bytes, peak {peak} (one gradient: {4 * n})")
+    assert opsd[grad_to].grad is not None and opsd[1 - grad_to].grad is None
+    assert kept == 4 * n and peak < 8 * n, (kept, peak)
 
 
 # ---- layouts of the loss operands -------------------------------------------------------------------------------------------------------

@@ -371,6 +371,30 @@ def test_gauss_cond_philox_noise_equals_given_noise(c, c0, ctot):
     lik_gate(f"gauss_cond philox C={c} lik_noisy", outs[1][1], R.gaussian_likelihood(d["y"].double() + nz.double(), d["mu"].double(), d["sigma"].double()))
 
 
+@pytest.mark.parametrize("shape", [(2, 6, 4, 4), (1, 8, 3, 5)], ids=["scalar", "vector"])
+def test_gauss_cond_wrapper_philox_equals_given_noise(shape):
+    """HF.gauss_cond drawing its noise in the kernel (philox_state) against the same call given crdr_philox_uniform's samples for the pair
+    the call forks (the state as it stands before the call): every output and all three gradients bit-equal; the state moves on by the
+    fork's increment, numel / 4 rounded up, plus one."""
+    L, lib, ops = hip()
+    n, c, h, w = shape
+    d = R.gc_case("gcd.dispatch.%d" % c, n, c, h, w)
+    st = philox_state()
+    nz = torch.empty(n, h, w, c, dtype=F32, device=dev())
+    L.check(lib.crdr_philox_uniform(st.data_ptr(), n, h * w, c, c, 0, nz.data_ptr(), c, ops._stream()), "philox_uniform")
+    gb, gyh = d["gbits"].to(dev()), cl(d["gyh"])
+    res = []
+    for src in ({"philox_state": st}, {"noise": nz.permute(0, 3, 1, 2)}):
+        leaves = [cl(d[k]).requires_grad_(True) for k in ("y", "mu", "sigma")]
+        out = HF().gauss_cond(*leaves, src.get("noise"), 0.11, 1e-9, True, philox_state=src.get("philox_state"))
+        ((out[1] * gb).sum() + (out[0] * gyh).sum()).backward()
+        res.append(list(out) + [t.grad for t in leaves])
+    assert st.tolist() == [R.PHILOX_SEED, R.PHILOX_OFFSET + (n * c * h * w + 3) // 4 + 1]
+    for nm, a, b in zip(("y_hat", "bits_noisy", "bits_quant", "lik_noisy", "lik_quant", "dy", "dmu", "dsigma"), *res):
+        assert a is not None and b is not None, nm
+        exact(f"gauss_cond wrapper {n}x{c}x{h}x{w} {nm}: in-kernel noise against given noise", a, b)
+
+
 # ---- entropy bottleneck ----------------------------------------------------------------------------------------------------------------
 
 def eb_module(sd, c):
