@@ -12,9 +12,12 @@
 // per pixel) runs on the fp32 matrix cores as a 1x1 launch of the implicit-GEMM kernel on x^2 and the rest are single-pass
 // elementwise kernels (16 B per lane).  Not on the CRDR training path -- the ELIC
 // transforms use ReLU bottlenecks -- so this is a registered optional op, parity-tested and profiled on its own.
+// The launches beyond 192 channels, in order: forward gdn_reparam, gdn_square, crdr_conv2d (1x1, bias = beta_eff: n), gdn_apply; backward the
+// first three again, gdn_bwd_prep, crdr_conv2d (w = gamma^T dn), gdn_bwd_finish, crdr_conv2d_wgrad on x^2, crdr_colsum, gdn_reparam_bwd.
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -767,6 +770,25 @@ struct GdnLayout {
   size_t conv_ws_bytes;
 };
 
+// the parametrisation's constants (the file's head): pedestal, lower bound of the stored beta, of the stored gamma
+struct GdnBounds { float ped, beta, gamma; };
+static GdnBounds gdn_bounds(const crdr_gdn_desc* d) {
+  const float ped = d->reparam_offset * d->reparam_offset;
+  return {ped, sqrtf(d->beta_min + ped), d->reparam_offset};
+}
+
+// The persistent kernels are built for NS = 4, 8 or 12 K steps of 16 channels (C <= 64, 128, 192; they work on 16 NS padded channels):
+// launch(std::integral_constant<int, NS>) for the class of C
+static int gdn_ns(int C) { return C <= 64 ? 4 : (C <= 128 ? 8 : 12); }
+template <class Launch>
+static void gdn_for_ns(int C, Launch&& launch) {
+  switch (gdn_ns(C)) {
+    case 4: launch(std::integral_constant<int, 4>{}); break;
+    case 8: launch(std::integral_constant<int, 8>{}); break;
+    default: launch(std::integral_constant<int, 12>{});
+  }
+}
+
 static int gdn_conv_desc(const crdr_gdn_desc* d, crdr_conv_desc* cd, int CP) {
   memset(cd, 0, sizeof(*cd));
   CRDR_REQUIRE(d->M > 0 && d->M < (1ll << 31), "gdn: pixel count out of range");
@@ -775,6 +797,17 @@ static int gdn_conv_desc(const crdr_gdn_desc* d, crdr_conv_desc* cd, int CP) {
   cd->ldx = d->C; cd->ldy = d->C; cd->wrows = CP; cd->wcols = CP;
   cd->flags = CRDR_CONV_NOSPLIT;   // the scratch of these launches is shared with other kernels: no ticket area
   return 0;
+}
+
+// the gamma gradient as a 1x1 weight gradient g = sum dn q: q = x^2 from the workspace, or (square_q) x itself, squared inside the kernel
+static crdr_wgrad_desc gdn_wgrad_desc(const crdr_gdn_desc* d, bool square_q) {
+  crdr_wgrad_desc wd;
+  memset(&wd, 0, sizeof(wd));
+  wd.N = (int32_t)d->M; wd.PH = 1; wd.PW = 1; wd.PC = d->C; wd.ldp = d->C; wd.QH = 1; wd.QW = 1; wd.QC = d->C;
+  wd.kh = 1; wd.kw = 1; wd.stride = 1; wd.pad = 0; wd.gI = d->C; wd.gJ = d->C;
+  wd.ldq = square_q ? d->ldx : d->C;
+  wd.algo = square_q ? CRDR_WGRAD_SQUARE_Q : 0;
+  return wd;
 }
 
 static int gdn_layout(const crdr_gdn_desc* d, int backward, GdnLayout* L) {
@@ -791,7 +824,7 @@ static int gdn_layout(const crdr_gdn_desc* d, int backward, GdnLayout* L) {
     L->dn = take(MC); L->u = take(MC); L->w = take(MC); L->dg = take((size_t)d->C * d->C); L->db = take(d->C);
     L->colpart = take((size_t)256 * CP);
     if (CP <= 192) {   // the persistent gamma-gradient kernel's per-workgroup partial sums
-      const int ch = CP <= 64 ? 64 : (CP <= 128 ? 128 : 192);
+      const int ch = 16 * gdn_ns(d->C);
       L->gpart = take((size_t)std::min<long long>((d->M + kGdnDgBP - 1) / kGdnDgBP, 256) * ch * ch);
     }
   }
@@ -799,13 +832,9 @@ static int gdn_layout(const crdr_gdn_desc* d, int backward, GdnLayout* L) {
   if (int rc = gdn_conv_desc(d, &cd, CP)) return rc;
   size_t cw = crdr_conv2d_workspace(&cd);
   if (backward) {
-    crdr_wgrad_desc wd;
-    memset(&wd, 0, sizeof(wd));
-    wd.N = (int32_t)d->M; wd.PH = 1; wd.PW = 1; wd.PC = d->C; wd.ldp = d->C; wd.QH = 1; wd.QW = 1; wd.QC = d->C; wd.ldq = d->C;
-    wd.kh = 1; wd.kw = 1; wd.stride = 1; wd.pad = 0; wd.gI = d->C; wd.gJ = d->C;
-    cw = std::max(cw, crdr_conv2d_wgrad_workspace(&wd));
-    wd.algo = CRDR_WGRAD_SQUARE_Q; wd.ldq = d->ldx;   // the fused backward's launch
-    cw = std::max(cw, crdr_conv2d_wgrad_workspace(&wd));
+    const crdr_wgrad_desc plain = gdn_wgrad_desc(d, false), squared = gdn_wgrad_desc(d, true);
+    cw = std::max(cw, crdr_conv2d_wgrad_workspace(&plain));
+    cw = std::max(cw, crdr_conv2d_wgrad_workspace(&squared));
     cw = std::max(cw, crdr_colsum_workspace(d->M, d->C));
   }
   L->conv_ws_bytes = cw;
@@ -814,14 +843,49 @@ static int gdn_layout(const crdr_gdn_desc* d, int backward, GdnLayout* L) {
   return 0;
 }
 
-// CRDR_GDN_UNFUSED_BWD=1: the nine-launch backward (the form the fused one is A/B-tested against; read at every call)
-static bool gdn_unfused_backward() {
-  const char* e = getenv("CRDR_GDN_UNFUSED_BWD");
-  return e && e[0] == '1';
+// the layout of a call's workspace, checked against what the caller brought
+static int gdn_bind(const crdr_gdn_desc* d, int backward, const void* ws, size_t ws_bytes, GdnLayout* L) {
+  if (int rc = gdn_layout(d, backward, L)) return rc;
+  CRDR_REQUIRE(ws_bytes >= L->end && (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "%s: workspace too small or misaligned (%zu < %zu)",
+               backward ? "gdn_bwd" : "gdn_fwd", ws_bytes, L->end);
+  return 0;
 }
 
-static bool gdn_fused_ok(const crdr_gdn_desc* d, const GdnLayout& L) {
-  return L.CP <= 192 && (long long)128 * d->ldx * 4 < (1ll << 31) && (long long)128 * d->ldy * 4 < (1ll << 31);
+// the fused kernels' descriptors span 128 pixel rows of every operand
+static bool gdn_rows_span(int ld) { return (long long)128 * ld * 4 < (1ll << 31); }
+static bool gdn_fused_ok(const crdr_gdn_desc* d, const GdnLayout& L) { return L.CP <= 192 && gdn_rows_span(d->ldx) && gdn_rows_span(d->ldy); }
+
+// the backward's route: the one-pass kernel where the forward's fused kernel runs and dy / dx fit its descriptors too, unless
+// CRDR_GDN_UNFUSED_BWD=1 asks for the nine-launch form (the one the fused backward is A/B-tested against; read at every call)
+static bool gdn_bwd_fused_route(const crdr_gdn_desc* d, const GdnLayout& L, int lddy, int lddx) {
+  if (!gdn_fused_ok(d, L) || !gdn_rows_span(lddy) || !gdn_rows_span(lddx)) return false;
+  const char* e = getenv("CRDR_GDN_UNFUSED_BWD");
+  return !(e && e[0] == '1');
+}
+
+// beta_eff and both packs of gamma_eff into the workspace (C x C, tiny)
+static int gdn_reparam(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, const float* beta, const float* gamma, crdr_stream_t s) {
+  const GdnBounds b = gdn_bounds(d);
+  hipLaunchKernelGGL(gdn_reparam_kernel, dim3(grid1((int64_t)L.CP * L.CP)), dim3(256), 0, as_stream(s), beta, gamma, d->C, L.CP, b.beta, b.gamma,
+                     b.ped, (float*)(ws + L.beta_eff), (float*)(ws + L.pack_f), (float*)(ws + L.pack_b));
+  CRDR_CHECK_LAUNCH("gdn_reparam");
+  return 0;
+}
+
+// the chain through the parametrisation of both effective gradients (the unfused forms leave them in the workspace)
+static int gdn_reparam_bwd(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, const float* beta, const float* gamma, float* dbeta, float* dgamma,
+                           crdr_stream_t s) {
+  const GdnBounds b = gdn_bounds(d);
+  hipLaunchKernelGGL(gdn_reparam_bwd_kernel, dim3(grid1((int64_t)d->C * d->C)), dim3(256), 0, as_stream(s), (const float*)(ws + L.dg),
+                     (const float*)(ws + L.db), gamma, beta, d->C, b.beta, b.gamma, dgamma, dbeta);
+  CRDR_CHECK_LAUNCH("gdn_reparam_bwd");
+  return 0;
+}
+
+static int gdn_square(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, const float* x, crdr_stream_t s) {
+  hipLaunchKernelGGL(gdn_square_kernel, dim3(grid1(d->M * (d->C / 4))), dim3(256), 0, as_stream(s), x, d->ldx, d->M, d->C / 4, (float*)(ws + L.x2));
+  CRDR_CHECK_LAUNCH("gdn_square");
+  return 0;
 }
 
 // y (mode 0) or n (mode 1) by the fused kernel; gamma_eff / beta_eff must already be in the workspace
@@ -832,32 +896,112 @@ static int gdn_fused(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, const
   a.tiles = (int)((d->M + kGdnBM - 1) / kGdnBM);
   a.CP = L.CP;
   a.x_bytes = 0; a.pack_bytes = (unsigned)((size_t)L.CP * L.CP * 4);
-  if (d->C <= 64) gdn_fused_launch<4>(a, as_stream(s));
-  else if (d->C <= 128) gdn_fused_launch<8>(a, as_stream(s));
-  else gdn_fused_launch<12>(a, as_stream(s));
+  gdn_for_ns(d->C, [&](auto ns) { gdn_fused_launch<decltype(ns)::value>(a, as_stream(s)); });
   CRDR_CHECK_LAUNCH("gdn_fused_fwd");
   return 0;
 }
 
+// n into the workspace: reparametrisation, then one fused pass over x, or (C > 192) x^2 and the 1x1 launch with beta as its bias
 static int gdn_norm(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, const float* x, const float* beta, const float* gamma,
                     crdr_stream_t s) {
-  const float ped = d->reparam_offset * d->reparam_offset;
-  const float bb = sqrtf(d->beta_min + ped), bg = d->reparam_offset;
-  float* beta_eff = (float*)(ws + L.beta_eff);
-  hipLaunchKernelGGL(gdn_reparam_kernel, dim3(grid1((int64_t)L.CP * L.CP)), dim3(256), 0, as_stream(s), beta, gamma, d->C, L.CP, bb, bg,
-                     ped, beta_eff, (float*)(ws + L.pack_f), (float*)(ws + L.pack_b));
-  CRDR_CHECK_LAUNCH("gdn_reparam");
-  if (gdn_fused_ok(d, L)) return gdn_fused(d, L, ws, x, (float*)(ws + L.norm), d->C, 1, s);   // n in one pass over x
-  hipLaunchKernelGGL(gdn_square_kernel, dim3(grid1(d->M * (d->C / 4))), dim3(256), 0, as_stream(s), x, d->ldx, d->M, d->C / 4,
-                     (float*)(ws + L.x2));
-  CRDR_CHECK_LAUNCH("gdn_square");
+  if (int rc = gdn_reparam(d, L, ws, beta, gamma, s)) return rc;
+  if (gdn_fused_ok(d, L)) return gdn_fused(d, L, ws, x, (float*)(ws + L.norm), d->C, 1, s);
+  if (int rc = gdn_square(d, L, ws, x, s)) return rc;
   crdr_conv_desc cd;
   if (int rc = gdn_conv_desc(d, &cd, L.CP)) return rc;
   cd.flags |= CRDR_EPI_BIAS;
   crdr_conv_io io;
   memset(&io, 0, sizeof(io));
-  io.x = (const float*)(ws + L.x2); io.w = (const float*)(ws + L.pack_f); io.y = (float*)(ws + L.norm); io.bias = beta_eff;
+  io.x = (const float*)(ws + L.x2); io.w = (const float*)(ws + L.pack_f); io.y = (float*)(ws + L.norm); io.bias = (const float*)(ws + L.beta_eff);
   return crdr_conv2d(&cd, &io, ws + L.conv_ws, L.conv_ws_bytes, s);
+}
+
+// the operands of crdr_gdn_bwd
+struct GdnBwdIo {
+  const float *x, *beta, *gamma, *dy;
+  int lddy;
+  float* dx;
+  int lddx;
+  float *dbeta, *dgamma;
+};
+
+// fused route, the pass over (x, dy): dx to the caller, dn and the per-workgroup column sums of dn (*colparts rows) into the workspace
+static int gdn_bwd_onepass(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, const GdnBwdIo& io, int* colparts, crdr_stream_t s) {
+  GdnBwd1Args b;
+  memset(&b, 0, sizeof(b));
+  b.x = io.x; b.dy = io.dy; b.pack_f = (const float*)(ws + L.pack_f); b.pack_b = (const float*)(ws + L.pack_b); b.beta = (const float*)(ws + L.beta_eff);
+  b.dn = (float*)(ws + L.dn); b.dx = io.dx; b.colpart = (float*)(ws + L.colpart); b.M = d->M; b.C = d->C; b.CP = L.CP; b.ldx = d->ldx; b.lddy = io.lddy;
+  b.ld_dn = d->C; b.lddx = io.lddx;
+  b.inverse = d->inverse; b.tiles = (int)((d->M + kGdnBM - 1) / kGdnBM); b.pack_bytes = (unsigned)((size_t)L.CP * L.CP * 4);
+  gdn_for_ns(d->C, [&](auto ns) { gdn_bwd1_launch<decltype(ns)::value>(b, as_stream(s)); });
+  CRDR_CHECK_LAUNCH("gdn_bwd_onepass");
+  *colparts = std::min(b.tiles, 256);   // one row per workgroup of the pass
+  return 0;
+}
+
+// fused route, the gamma gradient by the persistent kernel: every workgroup's partial C x C sum, then the finish kernels add them and chain both
+// gradients through the parametrisation
+static int gdn_dgamma_persistent(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, const GdnBwdIo& io, int colparts, crdr_stream_t s) {
+  const GdnBounds b = gdn_bounds(d);
+  GdnDgArgs ga;
+  memset(&ga, 0, sizeof(ga));
+  ga.dn = (const float*)(ws + L.dn); ga.x = io.x; ga.part = (float*)(ws + L.gpart); ga.M = d->M; ga.C = d->C; ga.ld_dn = d->C; ga.ldx = d->ldx;
+  ga.tiles = (int)((d->M + kGdnDgBP - 1) / kGdnDgBP);
+  gdn_for_ns(d->C, [&](auto ns) { gdn_dgamma_launch<decltype(ns)::value>(ga, as_stream(s)); });
+  CRDR_CHECK_LAUNCH("gdn_dgamma");
+  hipLaunchKernelGGL(gdn_dgamma_finish_kernel, dim3((d->C * d->C + 63) / 64), dim3(256), 0, as_stream(s), (const float*)ga.part,
+                     gdn_dgamma_grid(ga.tiles), 16 * gdn_ns(d->C), io.gamma, d->C, b.gamma, io.dgamma);
+  CRDR_CHECK_LAUNCH("gdn_dgamma_finish");
+  hipLaunchKernelGGL(gdn_dbeta_finish_kernel, dim3((d->C + 31) / 32), dim3(256), 0, as_stream(s), (const float*)(ws + L.colpart), colparts, L.CP, d->C,
+                     io.beta, b.beta, io.dbeta);
+  CRDR_CHECK_LAUNCH("gdn_dbeta_finish");
+  return 0;
+}
+
+// fused route with CRDR_GDN_DGAMMA=wgrad: the gamma gradient by the tiled weight-gradient kernel (the form the persistent one is measured against)
+static int gdn_dgamma_wgrad(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, const GdnBwdIo& io, int colparts, crdr_stream_t s) {
+  const crdr_wgrad_desc wd = gdn_wgrad_desc(d, true);
+  if (int rc = crdr_conv2d_wgrad(&wd, (const float*)(ws + L.dn), io.x, (float*)(ws + L.dg), ws + L.conv_ws, L.conv_ws_bytes, s)) return rc;
+  hipLaunchKernelGGL(gdn_colpart_sum_kernel, dim3((d->C + 31) / 32), dim3(256), 0, as_stream(s), (const float*)(ws + L.colpart), colparts, L.CP, d->C,
+                     (float*)(ws + L.db));
+  CRDR_CHECK_LAUNCH("gdn_colpart_sum");
+  return gdn_reparam_bwd(d, L, ws, io.beta, io.gamma, io.dbeta, io.dgamma, s);
+}
+
+// reparametrisation, ONE pass over (x, dy) -> (dx, dn, column sums), the gamma gradient straight from (dn, x) with the square taken in the
+// kernel, the chain rule through the parametrisation
+static int gdn_bwd_fused(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, const GdnBwdIo& io, crdr_stream_t s) {
+  if (int rc = gdn_reparam(d, L, ws, io.beta, io.gamma, s)) return rc;
+  int colparts = 0;
+  if (int rc = gdn_bwd_onepass(d, L, ws, io, &colparts, s)) return rc;
+  const char* via = getenv("CRDR_GDN_DGAMMA");   // (read at every call)
+  return (via && via[0] == 'w') ? gdn_dgamma_wgrad(d, L, ws, io, colparts, s) : gdn_dgamma_persistent(d, L, ws, io, colparts, s);
+}
+
+// the nine-launch form, and the only one beyond 192 channels: n (recomputed: cheaper than keeping M x C floats alive), dn and u, w = gamma^T dn
+// by a 1x1 launch, dx, the gamma gradient by the weight-gradient kernel on x^2, the beta gradient as column sums of dn, the chain rule
+static int gdn_bwd_unfused(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, const GdnBwdIo& io, crdr_stream_t s) {
+  if (int rc = gdn_norm(d, L, ws, io.x, io.beta, io.gamma, s)) return rc;
+  const int g = grid1(d->M * (d->C / 4));
+  float *dn = (float*)(ws + L.dn), *u = (float*)(ws + L.u), *w = (float*)(ws + L.w);
+  hipLaunchKernelGGL(gdn_bwd_prep_kernel, dim3(g), dim3(256), 0, as_stream(s), io.x, d->ldx, (const float*)(ws + L.norm), io.dy, io.lddy, d->M,
+                     d->C / 4, d->inverse, dn, u);
+  CRDR_CHECK_LAUNCH("gdn_bwd_prep");
+  crdr_conv_desc cd;
+  if (int rc = gdn_conv_desc(d, &cd, L.CP)) return rc;
+  crdr_conv_io cio;
+  memset(&cio, 0, sizeof(cio));
+  cio.x = dn; cio.w = (const float*)(ws + L.pack_b); cio.y = w;
+  if (int rc = crdr_conv2d(&cd, &cio, ws + L.conv_ws, L.conv_ws_bytes, s)) return rc;  // w[p][j] = sum_i gamma_ij dn[p][i]
+  hipLaunchKernelGGL(gdn_bwd_finish_kernel, dim3(g), dim3(256), 0, as_stream(s), io.x, d->ldx, (const float*)u, (const float*)w, d->M,
+                     d->C / 4, io.dx, io.lddx);
+  CRDR_CHECK_LAUNCH("gdn_bwd_finish");
+  if (gdn_fused_ok(d, L))   // the fused norm pass squares on the fly: the weight gradient still wants x^2 in memory
+    if (int rc = gdn_square(d, L, ws, io.x, s)) return rc;
+  const crdr_wgrad_desc wd = gdn_wgrad_desc(d, false);
+  if (int rc = crdr_conv2d_wgrad(&wd, dn, (const float*)(ws + L.x2), (float*)(ws + L.dg), ws + L.conv_ws, L.conv_ws_bytes, s)) return rc;
+  if (int rc = crdr_colsum(dn, d->C, d->M, d->C, (float*)(ws + L.db), 0, ws + L.conv_ws, L.conv_ws_bytes, s)) return rc;
+  return gdn_reparam_bwd(d, L, ws, io.beta, io.gamma, io.dbeta, io.dgamma, s);
 }
 
 }  // namespace crdr
@@ -874,15 +1018,11 @@ extern "C" int crdr_gdn_fwd(const crdr_gdn_desc* d, const float* x, const float*
                             size_t ws_bytes, crdr_stream_t s) {
   CRDR_REQUIRE(d && x && beta && gamma && y && ws, "gdn_fwd: null pointer");
   GdnLayout L;
-  if (int rc = gdn_layout(d, 0, &L)) return rc;
-  CRDR_REQUIRE(ws_bytes >= L.end && (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "gdn_fwd: workspace too small or misaligned (%zu < %zu)", ws_bytes, L.end);
+  if (int rc = gdn_bind(d, 0, ws, ws_bytes, &L)) return rc;
   CRDR_REQUIRE(d->ldy % 4 == 0 && d->ldy >= d->C, "gdn_fwd: ldy");
   char* w8 = (char*)ws;
-  if (gdn_fused_ok(d, L)) {   // reparametrisation (C x C, tiny) + ONE pass over x
-    const float ped = d->reparam_offset * d->reparam_offset;
-    hipLaunchKernelGGL(gdn_reparam_kernel, dim3(grid1((int64_t)L.CP * L.CP)), dim3(256), 0, as_stream(s), beta, gamma, d->C, L.CP,
-                       sqrtf(d->beta_min + ped), d->reparam_offset, ped, (float*)(w8 + L.beta_eff), (float*)(w8 + L.pack_f), (float*)(w8 + L.pack_b));
-    CRDR_CHECK_LAUNCH("gdn_reparam");
+  if (gdn_fused_ok(d, L)) {   // reparametrisation + ONE pass over x
+    if (int rc = gdn_reparam(d, L, w8, beta, gamma, s)) return rc;
     return gdn_fused(d, L, w8, x, y, d->ldy, 0, s);
   }
   if (int rc = gdn_norm(d, L, w8, x, beta, gamma, s)) return rc;
@@ -896,86 +1036,8 @@ extern "C" int crdr_gdn_bwd(const crdr_gdn_desc* d, const float* x, const float*
                             float* dx, int lddx, float* dbeta, float* dgamma, void* ws, size_t ws_bytes, crdr_stream_t s) {
   CRDR_REQUIRE(d && x && beta && gamma && dy && dx && dbeta && dgamma && ws, "gdn_bwd: null pointer");
   GdnLayout L;
-  if (int rc = gdn_layout(d, 1, &L)) return rc;
-  CRDR_REQUIRE(ws_bytes >= L.end && (reinterpret_cast<uintptr_t>(ws) & 255) == 0, "gdn_bwd: workspace too small or misaligned (%zu < %zu)", ws_bytes, L.end);
+  if (int rc = gdn_bind(d, 1, ws, ws_bytes, &L)) return rc;
   CRDR_REQUIRE(lddy % 4 == 0 && lddx % 4 == 0, "gdn_bwd: strides must be multiples of 4");
-  char* w8 = (char*)ws;
-  crdr_wgrad_desc wd;
-  memset(&wd, 0, sizeof(wd));
-  wd.N = (int32_t)d->M; wd.PH = 1; wd.PW = 1; wd.PC = d->C; wd.ldp = d->C; wd.QH = 1; wd.QW = 1; wd.QC = d->C; wd.ldq = d->C;
-  wd.kh = 1; wd.kw = 1; wd.stride = 1; wd.pad = 0; wd.gI = d->C; wd.gJ = d->C; wd.accumulate = 0;
-  const float ped = d->reparam_offset * d->reparam_offset;
-  if (gdn_fused_ok(d, L) && (long long)128 * lddy * 4 < (1ll << 31) && (long long)128 * lddx * 4 < (1ll << 31) && !gdn_unfused_backward()) {
-    // reparametrisation, ONE pass over (x, dy) -> (dx, dn, column sums), the gamma gradient straight from (dn, x) with the square taken in the
-    // kernel, the chain rule through the parametrisation
-    hipLaunchKernelGGL(gdn_reparam_kernel, dim3(grid1((int64_t)L.CP * L.CP)), dim3(256), 0, as_stream(s), beta, gamma, d->C, L.CP,
-                       sqrtf(d->beta_min + ped), d->reparam_offset, ped, (float*)(w8 + L.beta_eff), (float*)(w8 + L.pack_f), (float*)(w8 + L.pack_b));
-    CRDR_CHECK_LAUNCH("gdn_reparam");
-    float *dn = (float*)(w8 + L.dn), *dg = (float*)(w8 + L.dg), *parts = (float*)(w8 + L.colpart);
-    GdnBwd1Args b;
-    memset(&b, 0, sizeof(b));
-    b.x = x; b.dy = dy; b.pack_f = (const float*)(w8 + L.pack_f); b.pack_b = (const float*)(w8 + L.pack_b); b.beta = (const float*)(w8 + L.beta_eff);
-    b.dn = dn; b.dx = dx; b.colpart = parts; b.M = d->M; b.C = d->C; b.CP = L.CP; b.ldx = d->ldx; b.lddy = lddy; b.ld_dn = d->C; b.lddx = lddx;
-    b.inverse = d->inverse; b.tiles = (int)((d->M + kGdnBM - 1) / kGdnBM); b.pack_bytes = (unsigned)((size_t)L.CP * L.CP * 4);
-    if (d->C <= 64) gdn_bwd1_launch<4>(b, as_stream(s));
-    else if (d->C <= 128) gdn_bwd1_launch<8>(b, as_stream(s));
-    else gdn_bwd1_launch<12>(b, as_stream(s));
-    CRDR_CHECK_LAUNCH("gdn_bwd_onepass");
-    const char* via = getenv("CRDR_GDN_DGAMMA");
-    if (via && via[0] == 'w') {   // CRDR_GDN_DGAMMA=wgrad: the gamma gradient by the tiled weight-gradient kernel (the form the persistent one is measured against)
-      wd.ldq = d->ldx; wd.algo = CRDR_WGRAD_SQUARE_Q;
-      if (int rc = crdr_conv2d_wgrad(&wd, dn, x, dg, w8 + L.conv_ws, L.conv_ws_bytes, s)) return rc;
-      float* db = (float*)(w8 + L.db);
-      hipLaunchKernelGGL(gdn_colpart_sum_kernel, dim3((d->C + 31) / 32), dim3(256), 0, as_stream(s), (const float*)parts, std::min(b.tiles, 256), L.CP,
-                         d->C, db);
-      CRDR_CHECK_LAUNCH("gdn_colpart_sum");
-      hipLaunchKernelGGL(gdn_reparam_bwd_kernel, dim3(grid1((int64_t)d->C * d->C)), dim3(256), 0, as_stream(s), (const float*)dg,
-                         (const float*)db, gamma, beta, d->C, sqrtf(d->beta_min + ped), d->reparam_offset, dgamma, dbeta);
-      CRDR_CHECK_LAUNCH("gdn_reparam_bwd");
-      return 0;
-    }
-    GdnDgArgs ga;
-    memset(&ga, 0, sizeof(ga));
-    ga.dn = dn; ga.x = x; ga.part = (float*)(w8 + L.gpart); ga.M = d->M; ga.C = d->C; ga.ld_dn = d->C; ga.ldx = d->ldx;
-    ga.tiles = (int)((d->M + kGdnDgBP - 1) / kGdnDgBP);
-    const int ch = d->C <= 64 ? 64 : (d->C <= 128 ? 128 : 192);
-    if (d->C <= 64) gdn_dgamma_launch<4>(ga, as_stream(s));
-    else if (d->C <= 128) gdn_dgamma_launch<8>(ga, as_stream(s));
-    else gdn_dgamma_launch<12>(ga, as_stream(s));
-    CRDR_CHECK_LAUNCH("gdn_dgamma");
-    hipLaunchKernelGGL(gdn_dgamma_finish_kernel, dim3((d->C * d->C + 63) / 64), dim3(256), 0, as_stream(s), (const float*)ga.part,
-                       gdn_dgamma_grid(ga.tiles), ch, gamma, d->C, d->reparam_offset, dgamma);
-    CRDR_CHECK_LAUNCH("gdn_dgamma_finish");
-    hipLaunchKernelGGL(gdn_dbeta_finish_kernel, dim3((d->C + 31) / 32), dim3(256), 0, as_stream(s), (const float*)parts, std::min(b.tiles, 256), L.CP,
-                       d->C, beta, sqrtf(d->beta_min + ped), dbeta);
-    CRDR_CHECK_LAUNCH("gdn_dbeta_finish");
-    return 0;
-  }
-  if (int rc = gdn_norm(d, L, w8, x, beta, gamma, s)) return rc;  // recomputed: cheaper than keeping M x C floats alive
-  const int g = grid1(d->M * (d->C / 4));
-  float *dn = (float*)(w8 + L.dn), *u = (float*)(w8 + L.u), *w = (float*)(w8 + L.w);
-  hipLaunchKernelGGL(gdn_bwd_prep_kernel, dim3(g), dim3(256), 0, as_stream(s), x, d->ldx, (const float*)(w8 + L.norm), dy, lddy, d->M,
-                     d->C / 4, d->inverse, dn, u);
-  CRDR_CHECK_LAUNCH("gdn_bwd_prep");
-  crdr_conv_desc cd;
-  if (int rc = gdn_conv_desc(d, &cd, L.CP)) return rc;
-  crdr_conv_io io;
-  memset(&io, 0, sizeof(io));
-  io.x = dn; io.w = (const float*)(w8 + L.pack_b); io.y = w;
-  if (int rc = crdr_conv2d(&cd, &io, w8 + L.conv_ws, L.conv_ws_bytes, s)) return rc;  // w[p][j] = sum_i gamma_ij dn[p][i]
-  hipLaunchKernelGGL(gdn_bwd_finish_kernel, dim3(g), dim3(256), 0, as_stream(s), x, d->ldx, (const float*)u, (const float*)w, d->M,
-                     d->C / 4, dx, lddx);
-  CRDR_CHECK_LAUNCH("gdn_bwd_finish");
-  float *dg = (float*)(w8 + L.dg), *db = (float*)(w8 + L.db);
-  if (gdn_fused_ok(d, L)) {   // the fused norm pass squares on the fly: the weight gradient still wants x^2 in memory
-    hipLaunchKernelGGL(gdn_square_kernel, dim3(grid1(d->M * (d->C / 4))), dim3(256), 0, as_stream(s), x, d->ldx, d->M, d->C / 4,
-                       (float*)(w8 + L.x2));
-    CRDR_CHECK_LAUNCH("gdn_square");
-  }
-  if (int rc = crdr_conv2d_wgrad(&wd, dn, (const float*)(w8 + L.x2), dg, w8 + L.conv_ws, L.conv_ws_bytes, s)) return rc;
-  if (int rc = crdr_colsum(dn, d->C, d->M, d->C, db, 0, w8 + L.conv_ws, L.conv_ws_bytes, s)) return rc;
-  hipLaunchKernelGGL(gdn_reparam_bwd_kernel, dim3(grid1((int64_t)d->C * d->C)), dim3(256), 0, as_stream(s), (const float*)dg,
-                     (const float*)db, gamma, beta, d->C, sqrtf(d->beta_min + ped), d->reparam_offset, dgamma, dbeta);
-  CRDR_CHECK_LAUNCH("gdn_reparam_bwd");
-  return 0;
+  const GdnBwdIo io = {x, beta, gamma, dy, lddy, dx, lddx, dbeta, dgamma};
+  return gdn_bwd_fused_route(d, L, lddy, lddx) ? gdn_bwd_fused(d, L, (char*)ws, io, s) : gdn_bwd_unfused(d, L, (char*)ws, io, s);
 }

@@ -179,7 +179,7 @@ struct Plan {
   IgemmTaps t;
   int cfg;
   int stream;  // index into kStreamCfgs, or -1: the tiled kernel
-  int wino;    // 1 + variant: the Winograd kernel (wino.hip); cfg and stream are -1
+  WinoKernel wino;   // not None: a Winograd kernel (wino.hip, wino4.hip); cfg and stream are -1
   StreamArgs sa;
   dim3 grid;
   size_t lds;
@@ -277,7 +277,7 @@ static int plan_geometry(const crdr_conv_desc* d, Plan* pl, int G) {
   a.cs_ld = round_up(d->OC, 32);
   a.nsplit = 1;   // what the family's planner leaves alone: an unsplit launch without workspace, dynamic LDS or a grid of the plan's
   pl->cfg = pl->stream = -1;
-  pl->wino = 0;
+  pl->wino = WinoKernel::None;
   pl->grid = dim3(1, 1, 1);
   pl->lds = pl->ws_bytes = 0;
   return 0;
@@ -297,7 +297,7 @@ static int plan_wino(const crdr_conv_desc* d, Plan* pl, int G, const AlgoId& id,
     CRDR_REQUIRE(id.index == 0 || wino_pairs_ok(d), "conv2d: Winograd pair-tile variant: needs a channel tail of 1..32 and more than one patch");
     CRDR_REQUIRE(id.split == 0, "conv2d: the Winograd kernel has no split-K");
   }
-  pl->wino = f4 ? 3 : 1 + id.index;
+  pl->wino = f4 ? WinoKernel::F4 : (id.index == 1 ? WinoKernel::F2Pairs : WinoKernel::F2);
   pl->a.nsplit = nsplit;
   if (d->flags & CRDR_EPI_COLSUM) pl->a.cs_rows = f4 ? wino4_colsum_rows(d) : wino_colsum_rows(d);
   pl->ws_bytes = (size_t)CRDR_CONV_TICKETS * sizeof(int) + (f4 ? wino4_workspace(d, G, nsplit) : wino_workspace(d, G));
@@ -471,8 +471,9 @@ extern "C" int crdr_conv2d_colsum_layout(const crdr_conv_desc* d, int G, int* ro
 extern "C" int crdr_conv2d_choose_algo(const crdr_conv_desc* d, int G) {
   Plan pl;
   if (!d || build_plan(d, &pl, G)) return 0;
-  const AlgoFamily family = pl.wino == 3 ? kAlgoWino4 : (pl.wino ? kAlgoWino2 : (pl.stream >= 0 ? kAlgoStream : kAlgoTiled));
-  const int index = pl.wino == 3 ? 0 : (pl.wino ? pl.wino - 1 : (pl.stream >= 0 ? pl.stream : pl.cfg));
+  const bool f4 = pl.wino == WinoKernel::F4, f2 = pl.wino == WinoKernel::F2 || pl.wino == WinoKernel::F2Pairs;
+  const AlgoFamily family = f4 ? kAlgoWino4 : (f2 ? kAlgoWino2 : (pl.stream >= 0 ? kAlgoStream : kAlgoTiled));
+  const int index = f4 ? 0 : (f2 ? (pl.wino == WinoKernel::F2Pairs ? 1 : 0) : (pl.stream >= 0 ? pl.stream : pl.cfg));
   return conv_algo_encode(family, index, pl.a.nsplit, kNumCfgs, stream_num_variants());
 }
 
@@ -568,22 +569,24 @@ static int launch_conv(const crdr_conv_desc* d, const crdr_conv_io* ios, int G, 
   IgemmArgs& a = pl.a;
   a.vec_epi = vec_epi ? 1 : 0;
   a.fast_epi = fast_epilogue_ok(a, vec_epi) ? 1 : 0;
-  if (pl.wino) {
+  if (pl.wino != WinoKernel::None) {
+    const bool f4 = pl.wino == WinoKernel::F4;
     void* prof = profile_begin(as_stream(s));
-    if (pl.wino == 3) {
+    if (f4) {
       // transformed filters: in the workspace, or in the caller's buffer (crdr_conv2d_grouped_ex: kept across launches that share
       // weights -- `ucache_valid` skips the transform); the partial tiles of a split launch always live in the workspace
+      const size_t u_bytes = wino4_workspace(d, G, 1);
       float* u = (float*)ws + CRDR_CONV_TICKETS;
       if (ucache) {
-        CRDR_REQUIRE(ucache_bytes >= wino4_workspace(d, G, 1), "conv2d: filter cache of %zu bytes, the launch needs %zu", ucache_bytes, wino4_workspace(d, G, 1));
+        CRDR_REQUIRE(ucache_bytes >= u_bytes, "conv2d: filter cache of %zu bytes, the launch needs %zu", ucache_bytes, u_bytes);
         u = ucache;
       }
-      float* slabs = (float*)ws + CRDR_CONV_TICKETS + wino4_workspace(d, G, 1) / 4;
+      float* slabs = (float*)ws + CRDR_CONV_TICKETS + u_bytes / 4;
       if (int rc = wino4_launch(d, a, pl.t, grp, G, u, slabs, a.nsplit, ucache && ucache_valid, as_stream(s))) return rc;
-    } else if (int rc = wino_launch(d, pl.wino - 1, a, pl.t, grp, G, (float*)ws + CRDR_CONV_TICKETS, as_stream(s))) return rc;
+    } else if (int rc = wino_launch(d, pl.wino == WinoKernel::F2Pairs, a, pl.t, grp, G, (float*)ws + CRDR_CONV_TICKETS, as_stream(s))) return rc;
     // kind 3 / 5 / 6: filter transform + Winograd F(2x2, 3x3) / F(4x4, 3x3) kernel (6: a 5x5 stride-2 layer through it), direct-convolution
     // flop count
-    profile_end(pl.wino == 3 ? (d->kh == 5 ? 6 : 5) : 3, G * crdr_conv2d_flops(d), prof, as_stream(s));
+    profile_end(f4 ? (d->kh == 5 ? 6 : 5) : 3, G * crdr_conv2d_flops(d), prof, as_stream(s));
     return 0;
   }
   if (pl.stream >= 0) {
@@ -623,7 +626,7 @@ extern "C" int crdr_conv2d_grouped(const crdr_conv_desc* d, const crdr_conv_io* 
 
 extern "C" size_t crdr_conv2d_filter_cache_bytes(const crdr_conv_desc* d, int G) {
   Plan pl;
-  if (!d || G < 1 || G > CRDR_MAX_GROUP || build_plan(d, &pl, G) || pl.wino != 3) return 0;
+  if (!d || G < 1 || G > CRDR_MAX_GROUP || build_plan(d, &pl, G) || pl.wino != WinoKernel::F4) return 0;
   return wino4_workspace(d, G, 1);
 }
 
@@ -632,7 +635,7 @@ extern "C" int crdr_conv2d_filter_item(const crdr_conv_desc* d, int G, crdr_w4_f
   CRDR_REQUIRE(G >= 1 && G <= CRDR_MAX_GROUP, "conv2d_filter_item: %d problems (1..%d)", G, CRDR_MAX_GROUP);
   Plan pl;
   if (int rc = build_plan(d, &pl, G)) return rc;
-  CRDR_REQUIRE(pl.wino == 3, "conv2d_filter_item: the descriptor's `reserved` does not force the F(4x4, 3x3) kernel");
+  CRDR_REQUIRE(pl.wino == WinoKernel::F4, "conv2d_filter_item: the descriptor's `reserved` does not force the F(4x4, 3x3) kernel");
   return wino4_filter_item(d, pl.t, G, item);
 }
 

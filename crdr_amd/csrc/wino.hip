@@ -553,7 +553,23 @@ __global__ void wino_filter_kernel(const IgemmGroup grp, int ngroup, const float
 
 }  // namespace
 
-static int wino_ks(const crdr_conv_desc* d) { return d->kh == 5 ? 2 : 1; }   // sub-filters per axis
+// Everything about a launch that follows from the descriptor: filled once by wino_shape, read by every function below
+struct WinoShape {
+  int ks;                 // sub-filters per axis (a 5x5 kernel = 2 x 2 sub-filters of 3x3, the outer ones zero padded, 3 pixels apart)
+  int ntile, kchunks;     // N tiles of 64 output channels; chunks of 8 input channels
+  int GH, GW, patches;    // 16 x 16 output tiles down / across an image; of the launch = rows of its column-sum partials
+};
+
+static WinoShape wino_shape(const crdr_conv_desc* d) {
+  WinoShape s;
+  s.ks = d->kh == 5 ? 2 : 1;
+  s.ntile = cdiv(d->OC, 64);
+  s.kchunks = cdiv(d->C, 8);
+  s.GH = cdiv(d->OH, 16);
+  s.GW = cdiv(d->OW, 16);
+  s.patches = d->N * s.GH * s.GW;
+  return s;
+}
 
 bool wino_eligible(const crdr_conv_desc* d, int G) {
   if (!((d->kh == 3 && d->kw == 3) || (d->kh == 5 && d->kw == 5)) || d->stride != 1 || d->wlayout != 0) return false;
@@ -562,72 +578,74 @@ bool wino_eligible(const crdr_conv_desc* d, int G) {
   if (d->OH != d->H + grow || d->OW != d->W + grow) return false;
   if (d->pad < 0 || d->pad > k - 1) return false;
   if (d->C % 4 != 0 || d->ldx % 4 != 0) return false;
-  if (d->flags & (CRDR_EPI_GATE | CRDR_EPI_PREADD | CRDR_CONV_BF16X3)) return false;
-  if (G > 1 && (d->flags & (CRDR_EPI_VEC2 | CRDR_EPI_AFFINE | CRDR_EPI_MASKOFF))) return false;
-  const long long img = ((long long)d->N * d->H + 8) * d->W * d->ldx * 4;   // one descriptor spans the whole input tensor
+  if (!wino_admits(d, G)) return false;
+  // the descriptors of y / res / mask are based at a tile's first pixel and span the rest of that ONE image (wino_finish: desc)
   const long long oimg = (long long)d->OH * d->OW * std::max(std::max(d->ldy, d->ldres), d->ldmask) * 4;
-  if (img >= (1ll << 31) || oimg >= (1ll << 31)) return false;
+  if (oimg >= (1ll << 31)) return false;
   if ((long long)wino_workspace(d, G) / G >= (1ll << 31)) return false;
   return true;
 }
 
 size_t wino_workspace(const crdr_conv_desc* d, int G) {
-  return (size_t)G * cdiv(d->OC, 64) * wino_ks(d) * wino_ks(d) * cdiv(d->C, 8) * kUSlots * 16;
+  const WinoShape sh = wino_shape(d);
+  return (size_t)G * sh.ntile * sh.ks * sh.ks * sh.kchunks * kUSlots * 16;
 }
 
-int wino_colsum_rows(const crdr_conv_desc* d) { return d->N * cdiv(d->OH, 16) * cdiv(d->OW, 16); }
+int wino_colsum_rows(const crdr_conv_desc* d) { return wino_shape(d).patches; }
 
-// variant 1 (pair tiles): the channel count leaves a tail of <= 32 and there is more than one patch to pair
+// pair tiles: the channel count leaves a tail of <= 32 and there is more than one patch to pair
 bool wino_pairs_ok(const crdr_conv_desc* d) {
   const int tail = d->OC % 64;
-  return tail > 0 && tail <= 32 && d->N * cdiv(d->OH, 16) * cdiv(d->OW, 16) > 1;
+  return tail > 0 && tail <= 32 && wino_shape(d).patches > 1;
+}
+
+// m_inner: the patches of one N tile run together and share its filter blocks in L2 -- where the transformed filters are large (>= 32 MB) and
+// at least four times the input (the hoisted Charm convolutions); the same rule as the tiled kernel's (igemm.hip, plan_tiled)
+static int wino_m_inner(const crdr_conv_desc* d, int G) {
+  const double A = (double)d->N * d->H * d->W * d->C * 4.0, B = (double)wino_workspace(d, 1);
+  return (G == 1 && B >= 32.0e6 && A * 4.0 <= B) ? 1 : 0;
+}
+
+template <bool PAIRS>
+static void wino_launch_kernel(const IgemmArgs& a, const IgemmGroup& grp, int total, int gx, int gyn, int npair, int G, hipStream_t s) {
+  static std::atomic<bool> attr_done;
+  allow_full_lds(attr_done, wino_kernel<PAIRS>);
+  const size_t lds = (size_t)(WinoLds<PAIRS>::kTileFloats + 4 * 64 + 8 * 2 * 32) * sizeof(float);
+  hipLaunchKernelGGL(wino_kernel<PAIRS>, dim3(std::min(total, cu_count())), dim3(kNT), lds, s, a, grp, gx, gyn, npair, G);
 }
 
 // a: the argument block of the implicit-GEMM plan with every pointer / stride / flag filled in; taps: the plan's tap table
-int wino_launch(const crdr_conv_desc* d, int variant, IgemmArgs a, const IgemmTaps& taps, const IgemmGroup& grp, int G, float* u, hipStream_t s) {
+int wino_launch(const crdr_conv_desc* d, bool pairs, IgemmArgs a, const IgemmTaps& taps, const IgemmGroup& grp, int G, float* u, hipStream_t s) {
   CRDR_REQUIRE(wino_eligible(d, G), "conv2d: the Winograd kernel takes 3x3 / 5x5 stride-1 convolutions (C %% 4 == 0, no gate / pre-add epilogue)");
-  const int ks = wino_ks(d), kk = d->kh, nt = kk * kk;
+  const WinoShape sh = wino_shape(d);
+  const int ks = sh.ks, kk = d->kh, nt = kk * kk;
   WinoTaps wt;
   int dmin, win[25];
   if (int rc = tap_window(taps, kk, "Winograd", true, win, &dmin)) return rc;
   for (int t = 0; t < 36; ++t) wt.widx[t] = -1;
   for (int t = 0; t < nt; ++t) wt.widx[(t / kk) * (3 * ks) + t % kk] = win[t];
-  const int ntile = cdiv(d->OC, 64), kchunks = cdiv(d->C, 8);
   {
-    const long long total = (long long)ntile * ks * ks * kchunks * 128;
-    hipLaunchKernelGGL(wino_filter_kernel, dim3((unsigned)cdiv64(total, 256), G), dim3(256), 0, s, grp, G, a.w, u, d->C, d->OC, d->wrows, d->wcols, kchunks,
-                       ntile, ks, wt);
+    const long long total = (long long)sh.ntile * ks * ks * sh.kchunks * 128;
+    hipLaunchKernelGGL(wino_filter_kernel, dim3((unsigned)cdiv64(total, 256), G), dim3(256), 0, s, grp, G, a.w, u, d->C, d->OC, d->wrows, d->wcols,
+                       sh.kchunks, sh.ntile, ks, wt);
     CRDR_CHECK_LAUNCH("wino_filter_kernel");
   }
   a.w = u;
-  a.kchunks = kchunks;
-  {
-    const double A = (double)d->N * d->H * d->W * d->C * 4.0, B = (double)wino_workspace(d, 1);
-    a.m_inner = (G == 1 && B >= 32.0e6 && A * 4.0 <= B) ? 1 : 0;
-  }
-  a.nphase = ks * ks;   // sub-filters (a 5x5 kernel = 2 x 2 sub-filters of 3x3, the outer ones zero padded, 3 pixels apart)
+  a.kchunks = sh.kchunks;
+  a.m_inner = wino_m_inner(d, G);
+  a.nphase = ks * ks;   // sub-filters the K loop accumulates
   a.so = ks;
-  a.GH = cdiv(d->OH, 16);
-  a.GW = cdiv(d->OW, 16);
+  a.GH = sh.GH;
+  a.GW = sh.GW;
   a.si = -dmin;   // the patch starts `si` pixels above / left of its first output pixel
-  a.cs_rows = wino_colsum_rows(d);
-  const int ncu = cu_count();
-  // N tiles: full 64-channel ones, then either one padded tile for the tail (variant 0) or pair tiles (variant 1, two patches each)
-  const int gx = d->N * a.GH * a.GW;
-  const bool pairs = variant == 1;
+  a.cs_rows = sh.patches;
+  // N tiles: full 64-channel ones, then either one padded tile for the tail or pair tiles (two patches each)
+  const int gx = sh.patches;
   CRDR_REQUIRE(!pairs || wino_pairs_ok(d), "conv2d: Winograd pair-tile variant: needs a channel tail of 1..32 and more than one patch");
-  const int gyn = pairs ? d->OC / 64 : ntile, npair = pairs ? (gx + 1) / 2 : 0;
+  const int gyn = pairs ? d->OC / 64 : sh.ntile, npair = pairs ? (gx + 1) / 2 : 0;
   const int total = (gx * gyn + npair) * G;
-  static std::atomic<bool> attr_done[2];
-  if (pairs) allow_full_lds(attr_done[1], wino_kernel<true>);
-  else allow_full_lds(attr_done[0], wino_kernel<false>);
-  if (pairs) {
-    const size_t lds = (size_t)(WinoLds<true>::kTileFloats + 4 * 64 + 8 * 2 * 32) * sizeof(float);
-    hipLaunchKernelGGL(wino_kernel<true>, dim3(std::min(total, ncu)), dim3(kNT), lds, s, a, grp, gx, gyn, npair, G);
-  } else {
-    const size_t lds = (size_t)(WinoLds<false>::kTileFloats + 4 * 64 + 8 * 2 * 32) * sizeof(float);
-    hipLaunchKernelGGL(wino_kernel<false>, dim3(std::min(total, ncu)), dim3(kNT), lds, s, a, grp, gx, gyn, npair, G);
-  }
+  if (pairs) wino_launch_kernel<true>(a, grp, total, gx, gyn, npair, G, s);
+  else wino_launch_kernel<false>(a, grp, total, gx, gyn, npair, G, s);
   CRDR_CHECK_LAUNCH("wino_kernel");
   return 0;
 }

@@ -24,13 +24,25 @@ inline int tap_window(const IgemmTaps& taps, int k, const char* who, bool comple
   return 0;
 }
 
+// What both Winograd kernels ask of a launch beyond its shape: no gate / pre-add / split-bf16 epilogue, no epilogue operand that a grouped launch
+// cannot take per problem, and an input tensor (with the 8 rows a patch may reach past it) that one 2 GiB buffer descriptor spans.  The outputs'
+// extents are checked per kernel: the two base their descriptors differently.
+inline bool wino_admits(const crdr_conv_desc* d, int G) {
+  if (d->flags & (CRDR_EPI_GATE | CRDR_EPI_PREADD | CRDR_CONV_BF16X3)) return false;
+  if (G > 1 && (d->flags & (CRDR_EPI_VEC2 | CRDR_EPI_AFFINE | CRDR_EPI_MASKOFF))) return false;
+  return ((long long)d->N * d->H + 8) * d->W * d->ldx * 4 < (1ll << 31);
+}
+
+// the Winograd kernel of a plan (igemm.hip: Plan::wino)
+enum class WinoKernel { None, F2, F2Pairs, F4 };
+
 bool wino_eligible(const crdr_conv_desc* d, int G);
 size_t wino_workspace(const crdr_conv_desc* d, int G);   // bytes of transformed filters
 int wino_colsum_rows(const crdr_conv_desc* d);
-bool wino_pairs_ok(const crdr_conv_desc* d);   // variant 1 applies
-int wino_launch(const crdr_conv_desc* d, int variant, IgemmArgs a, const IgemmTaps& taps, const IgemmGroup& grp, int G, float* u, hipStream_t s);
+bool wino_pairs_ok(const crdr_conv_desc* d);   // the pair-tile variant applies
+int wino_launch(const crdr_conv_desc* d, bool pairs, IgemmArgs a, const IgemmTaps& taps, const IgemmGroup& grp, int G, float* u, hipStream_t s);
 
-// Winograd F(4x4, 3x3) path (wino4.hip): variant 2 of the forced Winograd ids.  vec_ok: every operand row is 16-byte aligned (known at
+// Winograd F(4x4, 3x3) path (wino4.hip): the third of the forced Winograd ids.  vec_ok: every operand row is 16-byte aligned (known at
 // launch; planning passes true)
 bool wino4_eligible(const crdr_conv_desc* d, int G, bool vec_ok);
 size_t wino4_workspace(const crdr_conv_desc* d, int G, int nsplit);   // bytes of transformed filters (+ the partial tiles of a K-split launch)

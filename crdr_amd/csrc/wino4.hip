@@ -1,5 +1,5 @@
 // Winograd F(4x4, 3x3) convolution on the exact-fp32 matrix cores for the 3x3 stride-1 layers (and, as 3x3 pieces, the 5x5 stride-2 and
-// stride-1 layers: wino4_mode below; tile geometries: W4Geo; K splits inside the launch: wino4_finish)
+// stride-1 layers: wino4_form below; tile geometries: W4Geo; K splits inside the launch: wino4_finish)
 // (elic_layers.py:23-36, cheng_nlam.py:31-46, clic21_gvae_discriminator.py:27-40) and their input gradients:
 //   Y = A^T [ (G g G^T) . (B^T d B) ] A   with 6x6 transforms (Lavin & Gray 2016; interpolation points 0, +-3/4, +-5/4, inf since round 5:
 //   wino4_xform.hpp says why):
@@ -924,110 +924,119 @@ __global__ __launch_bounds__(256, kFilterBlocksPerCU) void wino4_filter_batched_
 
 }  // namespace
 
-// the forms the kernel takes: 0 = none, 1 = 3x3 stride 1 (conv or its transposed twin), 2 = 5x5 stride-2 conv (pad 2, even H / W: four
-// parity sub-filters of 3x3 accumulated), 3 = 5x5 stride-2 transposed conv (pad 2, output = 2 x input: four output phases, each a 3x3
-// stride-1 conv of the input -- elic_layers.py:14-21 up_conv, elic_autoencoder.py:42-52 and their input gradients), 4 = 5x5 stride 1 pad 2
+// the forms the kernel takes: K3S1 = 3x3 stride 1 (conv or its transposed twin), K5S2 = 5x5 stride-2 conv (pad 2, even H / W: four
+// parity sub-filters of 3x3 accumulated), K5S2T = 5x5 stride-2 transposed conv (pad 2, output = 2 x input: four output phases, each a 3x3
+// stride-1 conv of the input -- elic_layers.py:14-21 up_conv, elic_autoencoder.py:42-52 and their input gradients), K5S1 = 5x5 stride 1 pad 2
 // (conv or transposed twin: four 3x3 sub-filters over the taps 3 bi + a, 3 bj + b, the last row / column of the padded 6x6 being zero,
 // accumulated over patches displaced by (3 bi, 3 bj) -- the slice transforms of the context model,
 // minnen20_charm_context_model.py:26-38)
-static int wino4_mode(const crdr_conv_desc* d) {
-  if (d->wlayout != 0) return 0;
+enum class W4Form { None, K3S1, K5S2, K5S2T, K5S1 };
+
+static W4Form wino4_form(const crdr_conv_desc* d) {
+  if (d->wlayout != 0) return W4Form::None;
   if (d->kh == 3 && d->kw == 3 && d->stride == 1) {
     const int grow = d->transposed ? 2 - 2 * d->pad : 2 * d->pad - 2;   // (a stride-1 transposed conv = a conv with pad k - 1 - pad)
-    return (d->OH == d->H + grow && d->OW == d->W + grow && d->pad >= 0 && d->pad <= 2) ? 1 : 0;
+    return (d->OH == d->H + grow && d->OW == d->W + grow && d->pad >= 0 && d->pad <= 2) ? W4Form::K3S1 : W4Form::None;
   }
-  if (d->kh == 5 && d->kw == 5 && d->stride == 1 && d->pad == 2) return (d->OH == d->H && d->OW == d->W && d->C >= 12) ? 4 : 0;
+  if (d->kh == 5 && d->kw == 5 && d->stride == 1 && d->pad == 2) return (d->OH == d->H && d->OW == d->W && d->C >= 12) ? W4Form::K5S1 : W4Form::None;
   if (d->kh == 5 && d->kw == 5 && d->stride == 2 && d->pad == 2) {
-    if (!d->transposed) return (d->H % 2 == 0 && d->W % 2 == 0 && d->OH == d->H / 2 && d->OW == d->W / 2) ? 2 : 0;
-    return (d->OH == 2 * d->H && d->OW == 2 * d->W) ? 3 : 0;
+    if (!d->transposed) return (d->H % 2 == 0 && d->W % 2 == 0 && d->OH == d->H / 2 && d->OW == d->W / 2) ? W4Form::K5S2 : W4Form::None;
+    return (d->OH == 2 * d->H && d->OW == 2 * d->W) ? W4Form::K5S2T : W4Form::None;
   }
-  return 0;
+  return W4Form::None;
 }
 
-// tile geometry of a launch (W4Geo): by the width of the grid the tiles cover -- the output, or one output phase
-// (geometry 2 -- two whole images of <= 16 x 16 per tile -- for the stride-1 forms only)
-static int wino4_geo(const crdr_conv_desc* d, int mode) {
-  const int gh = mode == 3 ? d->H : d->OH, gw = mode == 3 ? d->W : d->OW;
-  if ((mode == 1 || mode == 4) && gh <= 16 && gw <= 16) return 2;
-  return gw <= 32 ? 1 : 0;
-}
-static int wino4_tile_rows(int geo) { return geo == 0 ? 8 : 16; }
-static int wino4_tile_cols(int geo) { return geo == 0 ? 64 : (geo == 1 ? 32 : 16); }
-// output tiles of a launch (per N tile and output phase) = rows of its column-sum partials
-static int wino4_patches(const crdr_conv_desc* d, int mode) {
-  const int geo = wino4_geo(d, mode), gh = mode == 3 ? d->H : d->OH, gw = mode == 3 ? d->W : d->OW;
-  if (geo == 2) return cdiv(d->N, 2);
-  return d->N * cdiv(gh, wino4_tile_rows(geo)) * cdiv(gw, wino4_tile_cols(geo));
+constexpr size_t kTileSlabBytes = 4 * 2 * 16 * 64 * 16;   // one tile's published partial result (K-split launches)
+
+// Everything about a launch that follows from (d, G): filled once by wino4_shape, read by every function below
+struct Wino4Shape {
+  W4Form form;
+  int geo, gh, gw;            // tile geometry (W4Geo) and the grid the tiles cover: the output, or one output phase
+  int tile_rows, tile_cols;   // output pixels of a tile (geometry 2: of each of its two images)
+  int GH, GW, patches;        // tiles down / across an image; output tiles per N tile and output phase
+  int ntile, kchunks;         // N tiles of 64 output channels; chunks of 4 input channels
+  int nvar, nsub, so;         // filter variants in the cache; those of them the K loop accumulates; output stride (so x so output phases)
+  long long tiles;            // tiles of the launch (each the ticket of its K splits)
+  size_t filter_bytes;        // transformed filters of all G problems
+};
+
+static Wino4Shape wino4_shape(const crdr_conv_desc* d, int G) {
+  constexpr int kRows[3] = {4 * W4Geo<0>::TY, 4 * W4Geo<1>::TY, 4 * W4Geo<2>::TY}, kCols[3] = {4 * W4Geo<0>::TX, 4 * W4Geo<1>::TX, 4 * W4Geo<2>::TX};
+  Wino4Shape s;
+  s.form = wino4_form(d);
+  const bool phases = s.form == W4Form::K5S2T, stride1 = s.form == W4Form::K3S1 || s.form == W4Form::K5S1;
+  const bool pieces = s.form == W4Form::K5S2 || s.form == W4Form::K5S2T || s.form == W4Form::K5S1;   // a 5x5 kernel as four 3x3 ones
+  s.gh = phases ? d->H : d->OH;
+  s.gw = phases ? d->W : d->OW;
+  // geometry by the width of the grid (geometry 2 -- two whole images of <= 16 x 16 per tile -- for the stride-1 forms only)
+  s.geo = (stride1 && s.gh <= 16 && s.gw <= 16) ? 2 : (s.gw <= 32 ? 1 : 0);
+  s.tile_rows = kRows[s.geo];
+  s.tile_cols = kCols[s.geo];
+  s.GH = s.geo == 2 ? 1 : cdiv(s.gh, s.tile_rows);
+  s.GW = s.geo == 2 ? 1 : cdiv(s.gw, s.tile_cols);
+  s.patches = s.geo == 2 ? cdiv(d->N, 2) : d->N * s.GH * s.GW;
+  s.ntile = cdiv(d->OC, kBN4);
+  s.kchunks = cdiv(d->C, 4);
+  s.nvar = pieces ? 4 : 1;               // parity or shifted sub-filters / output phases
+  s.nsub = pieces && !phases ? 4 : 1;    // (an output phase is a tile of its own)
+  s.so = phases ? 2 : 1;
+  s.tiles = (long long)s.patches * s.ntile * G * (s.so * s.so);
+  s.filter_bytes = (size_t)G * s.ntile * s.nvar * s.kchunks * kUSlots4 * 16;
+  return s;
 }
 
-static size_t wino4_filter_bytes(const crdr_conv_desc* d, int G) {
-  const int nvar = wino4_mode(d) >= 2 ? 4 : 1;   // parity or shifted sub-filters / output phases
-  return (size_t)G * cdiv(d->OC, kBN4) * nvar * cdiv(d->C, 4) * kUSlots4 * 16;
-}
-// tiles of a launch (each the ticket of its K splits) and bytes of one tile's published partial result
-static long long wino4_tiles(const crdr_conv_desc* d, int G) {
-  const int mode = wino4_mode(d);
-  return (long long)wino4_patches(d, mode) * cdiv(d->OC, kBN4) * G * (mode == 3 ? 4 : 1);
-}
-constexpr size_t kTileSlabBytes = 4 * 2 * 16 * 64 * 16;
-
-// K splits (1 = none): the K range of a tile -- p.kchunks sub-steps of 4 channels, sub-filters included -- in `nsplit` equal parts
+// K splits (1 = none): the K range of a tile -- kchunks x nsub sub-steps of 4 channels -- in `nsplit` equal parts
 bool wino4_split_ok(const crdr_conv_desc* d, int G, int nsplit) {
   if (nsplit == 1) return true;
   if (d->flags & CRDR_CONV_NOSPLIT) return false;   // (the caller's workspace has no zeroed ticket head)
-  const int mode = wino4_mode(d);
-  if (!mode || nsplit < 1 || nsplit > 16) return false;
-  const int nph = (mode == 2 || mode == 4) ? 4 : 1, Kc = cdiv(d->C, 4), K4 = Kc * nph, cnt = cdiv(K4, nsplit);
+  const Wino4Shape sh = wino4_shape(d, G);
+  if (sh.form == W4Form::None || nsplit < 1 || nsplit > 16) return false;
+  const int Kc = sh.kchunks, K4 = Kc * sh.nsub, cnt = cdiv(K4, nsplit);
   if (K4 - (nsplit - 1) * cnt < 1) return false;                       // every split has work
-  const long long tiles = wino4_tiles(d, G);
-  if (tiles > CRDR_CONV_TICKETS || tiles * nsplit * (long long)kTileSlabBytes >= (1ll << 31)) return false;
-  if (mode == 4)   // a work item's first three patches share one shifted sub-filter (their lane offsets are derived once)
+  if (sh.tiles > CRDR_CONV_TICKETS || sh.tiles * nsplit * (long long)kTileSlabBytes >= (1ll << 31)) return false;
+  if (sh.form == W4Form::K5S1)   // a work item's first three patches share one shifted sub-filter (their lane offsets are derived once)
     for (int ks = 1; ks < nsplit; ++ks)
       if ((ks * cnt) % Kc + 3 > Kc && (ks * cnt) % Kc != 0) return false;
   return true;
 }
 
 size_t wino4_workspace(const crdr_conv_desc* d, int G, int nsplit) {
-  return wino4_filter_bytes(d, G) + (nsplit > 1 ? (size_t)wino4_tiles(d, G) * nsplit * kTileSlabBytes : 0);
+  const Wino4Shape sh = wino4_shape(d, G);
+  return sh.filter_bytes + (nsplit > 1 ? (size_t)sh.tiles * nsplit * kTileSlabBytes : 0);
 }
 
 bool wino4_eligible(const crdr_conv_desc* d, int G, bool vec_ok) {
-  const int mode = wino4_mode(d);
-  if (!mode) return false;
+  const Wino4Shape sh = wino4_shape(d, G);
+  if (sh.form == W4Form::None) return false;
   if (d->C % 4 != 0 || d->ldx % 4 != 0 || d->OC % 4 != 0 || d->ldy % 4 != 0) return false;
-  {   // the 8 x 64 / 16 x 32 tile (of the output, or of one output phase) wants wide images; two-image tiles want both dimensions >= 9
-    const int gh = mode == 3 ? d->H : d->OH, gw = mode == 3 ? d->W : d->OW;
-    if (wino4_geo(d, mode) == 2 ? (gh < 9 || gw < 9) : gw < 24) return false;
-  }
+  // the 8 x 64 / 16 x 32 tile (of the output, or of one output phase) wants wide images; two-image tiles want both dimensions >= 9
+  if (sh.geo == 2 ? (sh.gh < 9 || sh.gw < 9) : sh.gw < 24) return false;
   if ((d->flags & CRDR_EPI_RES) && d->ldres % 4 != 0) return false;
   if ((d->flags & (CRDR_EPI_RELUMASK | CRDR_EPI_LRELUMASK)) && d->ldmask % 4 != 0) return false;
-  if (d->flags & (CRDR_EPI_GATE | CRDR_EPI_PREADD | CRDR_CONV_BF16X3)) return false;
-  if (G > 1 && (d->flags & (CRDR_EPI_VEC2 | CRDR_EPI_AFFINE | CRDR_EPI_MASKOFF))) return false;
-  if (!vec_ok) return false;
-  const long long img = ((long long)d->N * d->H + 8) * d->W * d->ldx * 4;   // one descriptor spans a whole tensor
+  if (!wino_admits(d, G) || !vec_ok) return false;
+  // the descriptors of y / res / mask are based at the tensor and span all N images (wino4_finish: tdesc)
   const long long oimg = (long long)d->N * d->OH * d->OW * std::max(std::max(d->ldy, d->ldres), d->ldmask) * 4;
-  if (img >= (1ll << 31) || oimg >= (1ll << 31)) return false;
-  if ((long long)wino4_filter_bytes(d, G) / G >= (1ll << 31)) return false;
+  if (oimg >= (1ll << 31)) return false;
+  if ((long long)sh.filter_bytes / G >= (1ll << 31)) return false;
   return true;
 }
 
-
+// rows of a launch's column-sum partials: one per output tile (and output phase)
 int wino4_colsum_rows(const crdr_conv_desc* d) {
-  const int mode = wino4_mode(d);
-  return wino4_patches(d, mode) * (mode == 3 ? 4 : 1);
+  const Wino4Shape sh = wino4_shape(d, 1);
+  return sh.patches * sh.so * sh.so;
 }
 
 // which weight-pack tap feeds element (a, b) of sub-filter / phase v, and how far above / left of its first output pixel the patch starts
-static int wino4_taps(const crdr_conv_desc* d, const IgemmTaps& taps, Wino4Taps& wt, int& si) {
-  const int mode = wino4_mode(d);
+static int wino4_taps(W4Form form, const IgemmTaps& taps, Wino4Taps& wt, int& si) {
   for (int v = 0; v < 4; ++v)
     for (int t = 0; t < 9; ++t) wt.widx[v][t] = -1;
   si = 1;
-  if (mode == 1) {
+  if (form == W4Form::K3S1) {
     int dmin;
     if (int rc = tap_window(taps, 3, "Winograd F(4x4)", true, wt.widx[0], &dmin)) return rc;
     si = -dmin;   // the patch starts `si` pixels above / left of its first output pixel
-  } else if (mode == 4) {
+  } else if (form == W4Form::K5S1) {
     // taps (dh, dw) relative to the window's first: sub-filter (bi, bj) element (a, b) = tap (3 bi + a, 3 bj + b), absent past the 5th
     int dmin, win[25];
     if (int rc = tap_window(taps, 5, "Winograd F(4x4)", false, win, &dmin)) return rc;
@@ -1035,7 +1044,7 @@ static int wino4_taps(const crdr_conv_desc* d, const IgemmTaps& taps, Wino4Taps&
       for (int dw = 0; dw < 5; ++dw)
         if (win[dh * 5 + dw] >= 0) wt.widx[(dh / 3) * 2 + dw / 3][(dh % 3) * 3 + dw % 3] = win[dh * 5 + dw];
     si = -dmin;
-  } else if (mode == 2) {
+  } else if (form == W4Form::K5S2) {
     // out[o] = sum_t w[t] x[2 o - 2 + t], t = 2 a + p: sub-filter (ph, pw) element (a, b) = w[2 a + ph][2 b + pw] over the parity plane
     // x[2 m + ph], a 3-tap 'pad 1' correlation; the pack's tap index of kernel element (r, s) is 5 r + s
     for (int sub = 0; sub < 4; ++sub)
@@ -1059,14 +1068,14 @@ static int wino4_taps(const crdr_conv_desc* d, const IgemmTaps& taps, Wino4Taps&
 // description of one filter cache for the batched rebuild (crdr_conv2d_filter_item): everything but the pointers
 int wino4_filter_item(const crdr_conv_desc* d, const IgemmTaps& taps, int G, crdr_w4_filter_item* it) {
   CRDR_REQUIRE(wino4_eligible(d, G, true), "conv2d_filter_item: not a convolution the F(4x4, 3x3) kernel takes");
+  const Wino4Shape sh = wino4_shape(d, G);
   Wino4Taps wt;
   int si = 1;
-  if (int rc = wino4_taps(d, taps, wt, si)) return rc;
-  const int mode = wino4_mode(d);
+  if (int rc = wino4_taps(sh.form, taps, wt, si)) return rc;
   for (int g = 0; g < CRDR_MAX_GROUP; ++g) it->w[g] = nullptr;
   it->u = nullptr;
   it->G = G; it->Cin = d->C; it->Cout = d->OC; it->wrows = d->wrows; it->wcols = d->wcols;
-  it->kchunks = cdiv(d->C, 4); it->ntile = cdiv(d->OC, kBN4); it->nvar = mode >= 2 ? 4 : 1;
+  it->kchunks = sh.kchunks; it->ntile = sh.ntile; it->nvar = sh.nvar;
   for (int v = 0; v < 4; ++v)
     for (int t = 0; t < 9; ++t) it->widx[v][t] = wt.widx[v][t];
   it->units = (long long)G * it->ntile * it->nvar * wino4_filter_runs(it->kchunks);   // work units of the batched rebuild: runs of 8 chunks
@@ -1081,58 +1090,75 @@ int wino4_filters_batched(const crdr_w4_filter_item* items, const long long* pre
   return 0;
 }
 
-int wino4_launch(const crdr_conv_desc* d, IgemmArgs a, const IgemmTaps& taps, const IgemmGroup& grp, int G, float* u, float* slabs, int nsplit,
-                 bool filters_ready, hipStream_t s) {
-  CRDR_REQUIRE(wino4_eligible(d, G, a.vec_epi != 0), "conv2d: the F(4x4, 3x3) Winograd kernel takes 3x3 / 5x5 stride-1 and 5x5 stride-2 (pad 2) convolutions of >= 24 "
-               "output (phase) columns (or whole images of 9..16 pixels a side) with C, OC %% 4 == 0, 16-byte aligned operand rows and no gate / pre-add epilogue");
-  const int mode = wino4_mode(d);
-  Wino4Taps wt;
-  int si = 1;
-  if (int rc = wino4_taps(d, taps, wt, si)) return rc;
-  const int nvar = mode >= 2 ? 4 : 1;
-  const int ntile = cdiv(d->OC, kBN4), kchunks = cdiv(d->C, 4);
-  if (!filters_ready) {   // (a caller that kept the transformed filters of these weights from an earlier launch skips this)
-    hipLaunchKernelGGL(wino4_filter_kernel, dim3((unsigned)(ntile * nvar * wino4_filter_runs(kchunks)), G), dim3(256), 0, s, grp, G, a.w, u, d->C, d->OC,
-                       d->wrows, d->wcols, kchunks, ntile, nvar, wt);
-    CRDR_CHECK_LAUNCH("wino4_filter_kernel");
-  }
+// ---- the steps of wino4_launch
+// the in-launch filter transform (a caller that kept the transformed filters of these weights from an earlier launch skips it)
+static int wino4_transform_filters(const crdr_conv_desc* d, const Wino4Shape& sh, const Wino4Taps& wt, const IgemmGroup& grp, int G, const float* w,
+                                   float* u, hipStream_t s) {
+  hipLaunchKernelGGL(wino4_filter_kernel, dim3((unsigned)(sh.ntile * sh.nvar * wino4_filter_runs(sh.kchunks)), G), dim3(256), 0, s, grp, G, w, u, d->C,
+                     d->OC, d->wrows, d->wcols, sh.kchunks, sh.ntile, sh.nvar, wt);
+  CRDR_CHECK_LAUNCH("wino4_filter_kernel");
+  return 0;
+}
+
+// what the kernel reads of the shape, into the argument block of the implicit-GEMM plan
+static void wino4_fill_args(IgemmArgs& a, const Wino4Shape& sh, float* u, float* slabs, int nsplit, int si) {
   a.w = u;
   a.nsplit = nsplit;
   a.ws = slabs;   // partial tiles of a split launch
-  a.ws_ld = (int)wino4_tiles(d, G);
-  a.nphase = (mode == 2 || mode == 4) ? 4 : 1;   // parity / shifted sub-filters the K loop accumulates
-  a.kchunks = kchunks * a.nphase;             // sub-steps of a tile
-  a.so = mode == 3 ? 2 : 1;                   // output stride (4 output phases = 4 tiles per patch and N tile)
-  const int gh = mode == 3 ? d->H : d->OH, gw = mode == 3 ? d->W : d->OW;   // the grid the 8 x 64 tiles cover
-  const int geo = wino4_geo(d, mode);
-  a.GH = geo == 2 ? 1 : cdiv(gh, wino4_tile_rows(geo));
-  a.GW = geo == 2 ? 1 : cdiv(gw, wino4_tile_cols(geo));
+  a.ws_ld = (int)sh.tiles;
+  a.nphase = sh.nsub;                 // parity / shifted sub-filters the K loop accumulates
+  a.kchunks = sh.kchunks * sh.nsub;   // sub-steps of a tile
+  a.so = sh.so;                       // output stride (4 output phases = 4 tiles per patch and N tile)
+  a.GH = sh.GH;
+  a.GW = sh.GW;
   a.si = si;
-  a.cs_rows = wino4_colsum_rows(d);
-  const int ncu = cu_count();
-  const int gx = wino4_patches(d, mode);
-  const int total = gx * ntile * G * a.so * a.so;
-  using Kern = void (*)(const IgemmArgs, const IgemmGroup, int, int, int);
+  a.cs_rows = sh.patches * sh.so * sh.so;
+}
+
+// Tile order by a traffic estimate (each XCD has its own 4 MB L2; an XCD's ~32 concurrent workgroups walk consecutive tiles).  Patch-major: the
+// input once, but every round of resident workgroups touches every filter block of the launch again on every XCD unless they all fit L2
+// together.  Filter-stationary: the filters once, the input once per (N tile, phase).  Returns true for filter-stationary; CRDR_W4_ORDER
+// (experiments: 0 patch-major, 1 filter-stationary) overrides the estimate.
+static bool wino4_filter_stationary(const crdr_conv_desc* d, const Wino4Shape& sh, int nsplit, int ncu) {
+  const int ksteps = sh.kchunks * sh.nsub;
+  const double u_bytes = (double)sh.ntile * sh.so * sh.so * ksteps * (kUSlots4 * 16.0), x_bytes = (double)d->N * d->H * d->W * d->C * 4.0;
+  const double ncombo = (double)sh.ntile * sh.so * sh.so, rounds = std::max(1.0, (double)sh.tiles * nsplit / std::max(ncu, 1));
+  const double est_patch = x_bytes + 8.0 * u_bytes * (u_bytes > 3.0e6 ? rounds : 1.0), est_fstat = u_bytes + ncombo * x_bytes;
+  static const int force_order = [] { const char* e = getenv("CRDR_W4_ORDER"); return e ? atoi(e) : -1; }();
+  return force_order >= 0 ? force_order == 1 : est_fstat < est_patch;
+}
+
+using Wino4Kern = void (*)(const IgemmArgs, const IgemmGroup, int, int, int);
+// the kernel of an (epilogue class, K-split, form, geometry), allowed the whole LDS
+static Wino4Kern wino4_choose_kernel(int flags, bool split, const Wino4Shape& sh) {
 #define W4_ROW(SP, F, E) {wino4_kernel<0, F, SP, E>, wino4_kernel<1, F, SP, E>, wino4_kernel<2, F, SP, E>}
 #define W4_CLS(E) {{W4_ROW(false, 0, E), W4_ROW(false, 1, E)}, {W4_ROW(true, 0, E), W4_ROW(true, 1, E)}}
-  static const Kern kerns[4][2][2][3] = {W4_CLS(0), W4_CLS(1), W4_CLS(2), W4_CLS(3)};   // [epilogue class][split][form][geometry]
+  static const Wino4Kern kerns[4][2][2][3] = {W4_CLS(0), W4_CLS(1), W4_CLS(2), W4_CLS(3)};   // [epilogue class][split][form][geometry]
 #undef W4_CLS
 #undef W4_ROW
   static std::atomic<bool> attr_done;   // (one flag for the whole table: the first launch lifts the limit of every form)
   allow_full_lds(attr_done, &kerns[0][0][0][0], 4 * 2 * 2 * 3);
+  return kerns[w4_epi_class(flags)][split ? 1 : 0][sh.form == W4Form::K5S1 ? 1 : 0][sh.geo];
+}
+
+int wino4_launch(const crdr_conv_desc* d, IgemmArgs a, const IgemmTaps& taps, const IgemmGroup& grp, int G, float* u, float* slabs, int nsplit,
+                 bool filters_ready, hipStream_t s) {
+  CRDR_REQUIRE(wino4_eligible(d, G, a.vec_epi != 0), "conv2d: the F(4x4, 3x3) Winograd kernel takes 3x3 / 5x5 stride-1 and 5x5 stride-2 (pad 2) convolutions of >= 24 "
+               "output (phase) columns (or whole images of 9..16 pixels a side) with C, OC %% 4 == 0, 16-byte aligned operand rows and no gate / pre-add epilogue");
+  const Wino4Shape sh = wino4_shape(d, G);
+  Wino4Taps wt;
+  int si = 1;
+  if (int rc = wino4_taps(sh.form, taps, wt, si)) return rc;
+  if (!filters_ready)
+    if (int rc = wino4_transform_filters(d, sh, wt, grp, G, a.w, u, s)) return rc;
+  wino4_fill_args(a, sh, u, slabs, nsplit, si);
+  const int ncu = cu_count();
+  const int gyn = wino4_filter_stationary(d, sh, nsplit, ncu) ? -sh.ntile : sh.ntile;   // (< 0: filter-stationary, wino4_tile)
+  const Wino4Kern kern = wino4_choose_kernel(a.flags, nsplit > 1, sh);
   const size_t lds = (size_t)(kLdsFloats4 + 2 * 4 * kBN4 + 4) * sizeof(float);   // (+ the split-K ticket flag)
-  // tile order by a traffic estimate (each XCD has its own 4 MB L2; an XCD's ~32 concurrent workgroups walk consecutive tiles).  Patch-major: the
-  // input once, but every round of resident workgroups touches every filter block of the launch again on every XCD unless they all fit L2
-  // together.  Filter-stationary: the filters once, the input once per (N tile, phase).
-  const double u_bytes = (double)ntile * a.so * a.so * a.kchunks * (kUSlots4 * 16.0), x_bytes = (double)d->N * d->H * d->W * d->C * 4.0;
-  const double ncombo = (double)ntile * a.so * a.so, rounds = std::max(1.0, (double)total * nsplit / std::max(ncu, 1));
-  const double est_patch = x_bytes + 8.0 * u_bytes * (u_bytes > 3.0e6 ? rounds : 1.0), est_fstat = u_bytes + ncombo * x_bytes;
-  static const int force_order = [] { const char* e = getenv("CRDR_W4_ORDER"); return e ? atoi(e) : -1; }();   // experiments: 0 patch-major, 1 filter-stationary
-  const int gyn_arg = (force_order >= 0 ? force_order == 1 : est_fstat < est_patch) ? -ntile : ntile;
-  hipLaunchKernelGGL(kerns[w4_epi_class(a.flags)][nsplit > 1 ? 1 : 0][mode == 4 ? 1 : 0][geo], dim3(std::min(total * nsplit, ncu)), dim3(kNT4), lds, s, a, grp, gx, gyn_arg, G);
+  hipLaunchKernelGGL(kern, dim3(std::min((int)sh.tiles * nsplit, ncu)), dim3(kNT4), lds, s, a, grp, sh.patches, gyn, G);
   CRDR_CHECK_LAUNCH("wino4_kernel");
   return 0;
 }
-
 
 }  // namespace crdr

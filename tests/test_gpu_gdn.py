@@ -230,3 +230,30 @@ def test_gdn_gamma_gradient_routes_agree(c, monkeypatch):
     via = run()
     assert torch.equal(own[0], via[0])   # dx does not depend on the route
     assert rel(own[1], via[1]) < 1e-6 and rel(own[2], via[2]) < 1e-5, (rel(own[1], via[1]), rel(own[2], via[2]))
+
+
+@pytest.mark.parametrize("inverse", [False, True])
+@pytest.mark.parametrize("c,n,h,w", [(224, 2, 9, 7), (196, 1, 5, 5)])
+def test_gdn_beyond_192_channels_vs_float64(inverse, c, n, h, w):
+    """Beyond 192 channels no fused kernel applies (gdn.hip: square -> 1x1 launch -> apply, and the nine-launch backward): 224 channels fill
+    the padded pack, 196 leave 28 padded columns of it (CP = 224).  Forward and all three gradients against float64: 2e-5 of the largest
+    reference value for y and dx, 5e-5 for dbeta and dgamma."""
+    from crdr_amd.models.layer.gdn import GDN
+    d = dev()
+    m = GDN(c, inverse=inverse)
+    g = torch.Generator().manual_seed(29 + c + int(inverse))
+    with torch.no_grad():
+        m.gamma.copy_(torch.sqrt(torch.rand(c, c, generator=g) * 0.02 + 2.0 ** -36))
+        m.beta.copy_(torch.sqrt(torch.rand(c, generator=g) + 0.5))
+    m.to(d)
+    x = (torch.randn(n, c, h, w, generator=g) * 2.0).to(d).contiguous(memory_format=torch.channels_last)
+    cot = torch.randn(n, c, h, w, generator=g).to(d).contiguous(memory_format=torch.channels_last)
+    ref = _gdn_f64(m, x, cot, inverse)
+    xd = x.clone().requires_grad_(True)
+    y = m(xd)
+    (y * cot).sum().backward()
+    got = (y.detach(), xd.grad, m.beta.grad, m.gamma.grad)
+    err = [float((a.double() - r).abs().max() / r.abs().max()) for a, r in zip(got, ref)]
+    print(f"gdn c={c} inverse={inverse}: max error / max reference: y {err[0]:.3g} dx {err[1]:.3g} dbeta {err[2]:.3g} dgamma {err[3]:.3g}")
+    for name, e, tol in zip(("y", "dx", "dbeta", "dgamma"), err, (2e-5, 2e-5, 5e-5, 5e-5)):
+        assert e < tol, (name, e)

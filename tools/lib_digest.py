@@ -6,7 +6,8 @@
     tune database (a 'c' key omits the weight pack's size: the packers' round32(OC) x round32(C), tap-major round32(4 taps) columns) and the
     shapes of tests/test_cabi_and_host.py's Winograd planning test, at G = 1, 3, 16; conv flags as shipped and with COLSUM, each also with
     NOSPLIT / BF16X3 / BF16X6; wgrad modes 0 / BF16X3 / BF16X6 / SQUARE_Q; algorithm id 0 and every base id up to two past the last one,
-    each with all sixteen values of bits 8..11.  Printed per requested family: records, records that planned, and one SHA-256 over all.
+    each with all sixteen values of bits 8..11; crdr_gdn_workspace (forward and backward) over M = 1 .. 262144, C = 4 .. 320 and
+    a dense or padded ldx.  Printed per requested family: records, records that planned, and one SHA-256 over all.
 Two builds compute the same plans and run the same device code when the two outputs are equal."""
 import argparse
 import ast
@@ -140,6 +141,12 @@ def sweep(lib):
                         # a successful plan that needs no workspace does not occur (a slab is never empty); a refusal leaves its text
                         ws = lib.crdr_conv2d_wgrad_grouped_workspace(p, G)
                         record("wgrad", wgrad_family(base), ws, [i, mode, G, d.algo, ws, ws or err()])
+    for m in (1, 63, 64, 65, 126, 4096, 32768, 262144):
+        for c in range(4, 321, 4):
+            for ldx in (c, c + 4):
+                d = L.GdnDesc(M=m, C=c, ldx=ldx, ldy=c, inverse=0, beta_min=1e-6, reparam_offset=2.0 ** -18)
+                ws = [lib.crdr_gdn_workspace(C.byref(d), backward) for backward in (0, 1)]
+                record("gdn", "workspace", all(ws), [m, c, ldx] + ws)
     return {"descriptors": {"conv": [fields(d) for d in convs], "wgrad": [fields(d)[:-1] for d in wgrads]},
             "families": {f"{side} {fam}": {"records": n, "planned": ok} for (side, fam), (n, ok) in sorted(stats.items())},
             "sha256": sha.hexdigest(), "skipped_keys": [repr(k) for k in bad]}
