@@ -6,15 +6,13 @@ to the kernels in place through its pixel stride (`ld`).  All arithmetic happens
 from __future__ import annotations
 
 import ctypes as C
-import functools
 import os
-import types
 from typing import Optional, Tuple
 
 import torch
 
 from . import lib as L
-from . import packs
+from . import packs, tune
 from .batched import BumpArena, JobTable, SiteTables, _capturing, _require_gpu, _stream  # noqa: F401  (the capture rules of the batched launches live there)
 
 _ws_cache = {}
@@ -41,70 +39,29 @@ MATRIX_BF16X3 = False
 MATRIX_BF16X6 = False
 
 
+def _matrix_mode() -> int:   # 0 exact fp32, 1 bf16x3, 2 bf16x6
+    return 2 if MATRIX_BF16X6 else (1 if MATRIX_BF16X3 else 0)
+
+
 def _cf() -> int:
-    return L.CONV_BF16X6 if MATRIX_BF16X6 else (L.CONV_BF16X3 if MATRIX_BF16X3 else 0)
+    return (0, L.CONV_BF16X3, L.CONV_BF16X6)[_matrix_mode()]
 
 
 def _wa(algo: int) -> int:
-    return int(algo) | (L.WGRAD_BF16X6 if MATRIX_BF16X6 else (L.WGRAD_BF16X3 if MATRIX_BF16X3 else 0))
+    return int(algo) | (0, L.WGRAD_BF16X3, L.WGRAD_BF16X6)[_matrix_mode()]
 
 
-def _mk() -> tuple:
-    """suffix of the weight-gradient tuner keys (the conv keys carry the mode in their flags)"""
-    return (2,) if MATRIX_BF16X6 else ((1,) if MATRIX_BF16X3 else ())
-_algo_cache = {}
-TUNE_LOG = []
+def _mk() -> tuple:   # suffix of the weight-gradient tuner keys (the conv keys carry the mode in their flags)
+    return ((), (1,), (2,))[_matrix_mode()]
 
 
-TUNE_ROUNDS = int(os.environ.get("CRDR_TUNE_ROUNDS", "1"))  # >1: best of several timings (perf-database builds)
-
-
-# CRDR_TUNE_COLD=1: evict L2 / Infinity Cache (a 512 MB read-modify-write) before every timed launch.  Inside a training step
-# a conv finds its weights and activations cold -- the producer ran on other XCDs, 100+ MB of other tensors ago -- while
-# back-to-back timing of one launch measures the cache-warm case, which favours configurations with more, smaller loads.
-TUNE_COLD = os.environ.get("CRDR_TUNE_COLD", "0") == "1"
-_evict = None
-
-
-def _time_call_cold(fn, reps: int = 2) -> float:
-    global _evict
-    if _evict is None:
-        _evict = torch.zeros(128 << 20, dtype=torch.float32, device="cuda")
-    fn()
-    best = float("inf")
-    for _ in range(max(1, TUNE_ROUNDS)):
-        tot = 0.0
-        for _ in range(reps):
-            _evict.add_(1.0)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            tot += e0.elapsed_time(e1)
-        best = min(best, tot / reps)
-    return best
-
-
-def _time_call(fn, reps: int = 2) -> float:
-    if TUNE_COLD:
-        return _time_call_cold(fn, reps)
-    fn()
-    best = float("inf")
-    for _ in range(max(1, TUNE_ROUNDS)):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(reps):
-            fn()
-        e1.record()
-        e1.synchronize()
-        best = min(best, e0.elapsed_time(e1) / reps)
-    return best
-
+# The tuner lives in tune.py.  bench.py reads these names as attributes of ops, so they stay bound here, to the SAME objects (tune only
+# mutates its containers); everything else says tune.<name>.
+_algo_cache, TUNE_LOG, TUNE_REJECTED = tune.algo_cache, tune.LOG, tune.REJECTED
+load_tune_cache, save_tune_cache, DEFAULT_TUNE_DB = tune.load, tune.save, tune.DEFAULT_DB
 
 WINOGRAD = os.environ.get("CRDR_WINOGRAD", "1") != "0"   # 0: the tuner never offers the Winograd kernel
 WINO4 = os.environ.get("CRDR_WINO4", "1") != "0"         # 0: ... never the F(4x4, 3x3) / F(3x3, 4x4) kernels (F(2x2) stays)
-
 
 # Tests: every convolution a Winograd kernel accepts takes it (without the tuner, whose choice is per shape and speed): the
 # model-level parity tests run once more through it.  True: the F(2x2, 3x3) kernel (variants 0 / 1); 4: the F(4x4, 3x3) kernel
@@ -112,27 +69,12 @@ WINO4 = os.environ.get("CRDR_WINO4", "1") != "0"         # 0: ... never the F(4x
 PREFER_WINOGRAD = False
 
 
-@functools.lru_cache(maxsize=None)
-def _ids():
-    """Where the kernel families sit among the forced-algorithm ids (layout: csrc/algo_id.hpp), read from the library once.  Library constants
-    only: what the switches WINOGRAD / WINO4 leave of them is decided where a list is asked for.  -1: the library has no such kernel.
-    (crdr_conv2d_wgrad_num_configs() counts the F(2x2) slab kernel: the F(4x4) one is the id behind it.)"""
-    lib = L.load()
-    n, ns, nw = lib.crdr_conv2d_num_configs(), lib.crdr_conv2d_num_stream_configs(), lib.crdr_conv2d_num_wino_configs()
-    return types.SimpleNamespace(stream=tuple(range(n + 1, n + 1 + ns)), wino=tuple(range(n + 1 + ns, n + 1 + ns + nw)), wino4=n + ns + 3 if nw > 2 else -1,
-                                 wgrad_wino4=lib.crdr_conv2d_wgrad_num_configs() + 1 if lib.crdr_conv2d_wgrad_num_wino_configs() >= 2 else -1)
-
-
-def tile_id(cfg: int, log2_split: int = 0) -> int:   # forced id of tile configuration `cfg` (conv or weight gradient) split 2^log2_split ways
-    return (cfg + 1) | (log2_split << 8)
-
-
 def _prefer_wino(d, G: int = 1) -> int:
     """-> the Winograd algorithm id if PREFER_WINOGRAD is set and the library accepts it for this launch, else 0."""
     if not PREFER_WINOGRAD or (d.kh, d.kw, d.stride) not in (((3, 3, 1), (5, 5, 1), (5, 5, 2)) if PREFER_WINOGRAD == 4 else ((3, 3, 1), (5, 5, 1))):
         return 0
     q = L.ConvDesc.from_buffer_copy(d)
-    for wid in reversed(_ids().wino if PREFER_WINOGRAD == 4 else _ids().wino[:2]):   # (F(4x4) / the pair-tile variant where they apply)
+    for wid in reversed(tune.ids().wino if PREFER_WINOGRAD == 4 else tune.ids().wino[:2]):   # (F(4x4) / the pair-tile variant where they apply)
         q.reserved = wid
         if L.load().crdr_conv2d_choose_algo(C.byref(q), G) == wid:
             return wid
@@ -145,8 +87,8 @@ WINO4_SPLITS = (1, 2, 3, 5, 7, 11, 15)
 def _wgrad_wino4_ids():
     """Forced ids of the F(3x3, 4x4) weight-gradient slab kernel (wino4_wgrad.hip: the id behind the last wgrad configuration) with its strip
     splits 1 .. 256; the library refuses them for the shapes it does not take."""
-    w4 = _ids().wgrad_wino4
-    return [tile_id(w4 - 1, ls) for ls in range(9)] if WINOGRAD and WINO4 and w4 >= 0 else []
+    w4 = tune.ids().wgrad_wino4
+    return [tune.tile_id(w4 - 1, ls) for ls in range(9)] if WINOGRAD and WINO4 and w4 >= 0 else []
 
 
 # Test hook: callable(weight, saved activation as an NCHW view, offset vector or None) called in grad mode by every fused conv / chain layer /
@@ -154,6 +96,11 @@ def _wgrad_wino4_ids():
 # with CRDR_EPI_MASKOFF, where a beta vector was added after the ReLU: act - offset > 0).  tests/test_gpu_step.py hands the generator's masks
 # to the oracle (oracle.relu / generator_forward(impose=...)).  None in production.
 RELU_MASK_SINK = None
+
+
+def _is_wino4(algo: int) -> bool:   # the F(4x4, 3x3) kernel, whatever K split the id carries in bits 8..11
+    return (algo & 0xFF) == tune.ids().wino4
+
 
 WINO4_DEMOTED = [0]   # launches whose tuned / preferred F(4x4) plan was dropped because an epilogue operand was not 16-byte aligned
 
@@ -163,20 +110,14 @@ def _demote_if_misaligned(d, ios, G: int, explicit: bool) -> None:
     and strides, not by pointer alignment: for an output / residual / mask view at a channel offset that is not a multiple of 4 floats the
     launch would be refused by the library (it hard-fails an id it cannot honour, which is right for an EXPLICITLY forced one).  Such a
     launch takes the built-in plan instead."""
-    if explicit or (d.reserved & 0xFF) != _ids().wino4:
-        return
-    for g in range(G):
-        for f_ in ("y", "res", "mask"):
-            p_ = getattr(ios[g], f_)
-            if p_ and int(p_) % 16:
-                d.reserved = 0
-                WINO4_DEMOTED[0] += 1
-                return
+    if not explicit and _is_wino4(d.reserved) and any(p_ and int(p_) % 16 for g in range(G) for p_ in (ios[g].y, ios[g].res, ios[g].mask)):
+        d.reserved = 0
+        WINO4_DEMOTED[0] += 1
 
 
 def _launch_conv(lib, d, ios, G: int, ws, ws_n, device):
     """crdr_conv2d_grouped, through the persistent filter cache (packs) where the launch runs the F(4x4) kernel on registered weight packs."""
-    cached = packs.filter_cache_for(d, ios, G, device) if (d.reserved & 0xFF) == _ids().wino4 else None
+    cached = packs.filter_cache_for(d, ios, G, device) if _is_wino4(d.reserved) else None
     if cached is None:
         return lib.crdr_conv2d_grouped(C.byref(d), ios, G, ws, ws_n, _stream())
     ent, valid = cached
@@ -187,7 +128,6 @@ def _launch_conv(lib, d, ios, G: int, ws, ws_n, device):
 # front of the convolution, so a candidate is timed with its filters in place (a scratch cache filled by the first trial launch) and charged
 # the share of the batched rebuild it causes: the cache's bytes at the rate that launch runs at (~4.8 GB per ms).
 _tune_filters = {}
-_tune_w4_penalty = [0.0]
 
 
 def _conv_workspace(lib, d, G: int, device):
@@ -195,140 +135,94 @@ def _conv_workspace(lib, d, G: int, device):
     return workspace(nb, device, conv=True) if nb else (None, 0)
 
 
-def _tune_conv_launch(lib, d, ios, G: int, device) -> bool:
-    _tune_w4_penalty[0] = 0.0
+def _tune_conv_launch(lib, d, ios, G: int, device) -> Tuple[bool, float]:   # -> (the library took it, ms of batched filter rebuild it is charged)
     w_, wn_ = _conv_workspace(lib, d, G, device)
-    nb = int(lib.crdr_conv2d_filter_cache_bytes(C.byref(d), G)) if (d.reserved & 0xFF) == _ids().wino4 else 0
+    nb = int(lib.crdr_conv2d_filter_cache_bytes(C.byref(d), G)) if _is_wino4(d.reserved) else 0
     if not nb or not packs.cacheable(ios, G) or _capturing():
         # (no transformed filters, or) the real launch will not find a cache (sub-block / temporary packs, or a launch first seen under
         # capture): it transforms on every call, and that is what the candidate is timed with
-        return lib.crdr_conv2d_grouped(C.byref(d), ios, G, w_, wn_, _stream()) == 0
+        return lib.crdr_conv2d_grouped(C.byref(d), ios, G, w_, wn_, _stream()) == 0, 0.0
     key = (packs.filter_key(d, ios, G), tuple(packs.version(int(ios[g].w)) for g in range(G)))
     ent = _tune_filters.get(key)
-    if ent is None or ent.numel() * 4 < nb:
+    valid = int(ent is not None and ent.numel() * 4 >= nb)
+    if not valid:
         _tune_filters.clear()   # (one shape is tuned at a time: the previous shape's scratch is garbage)
         ent = _tune_filters[key] = torch.empty(nb // 4, dtype=torch.float32, device=device)
-        valid = 0
-    else:
-        valid = 1
-    _tune_w4_penalty[0] = nb / 4.8e9
-    return lib.crdr_conv2d_grouped_ex(C.byref(d), ios, G, w_, wn_, ent.data_ptr(), nb, valid, _stream()) == 0
+    return lib.crdr_conv2d_grouped_ex(C.byref(d), ios, G, w_, wn_, ent.data_ptr(), nb, valid, _stream()) == 0, nb / 4.8e9
 
 
 def _stream_ids():
     """Forced-algorithm ids of the streaming 1x1 variants and of the Winograd 3x3 kernel (the library rejects them for other shapes)."""
-    ids = list(_ids().stream) + (list(_ids().wino if WINO4 else _ids().wino[:2]) if WINOGRAD else [])
-    if WINOGRAD and WINO4 and _ids().wino4 >= 0:   # the F(4x4) kernel with 2, 3, 4, 6, 8, 12 or 16 K splits per tile (bits 8..11 = splits - 1): launches with fewer tiles than CUs
-        ids += [_ids().wino4 | (v << 8) for v in WINO4_SPLITS]
+    ids = list(tune.ids().stream) + (list(tune.ids().wino if WINO4 else tune.ids().wino[:2]) if WINOGRAD else [])
+    if WINOGRAD and WINO4 and tune.ids().wino4 >= 0:   # the F(4x4) kernel with 2, 3, 4, 6, 8, 12 or 16 K splits per tile (bits 8..11 = splits - 1): launches with fewer tiles than CUs
+        ids += [tune.ids().wino4 | (v << 8) for v in WINO4_SPLITS]
     return ids
 
 
-# A candidate may only win if its result agrees with the baseline plan's (algo 0, the built-in plan the parity tests run) on the
-# very operands it is timed on: max |candidate - baseline| <= TUNE_AGREE[kind] x max |baseline|.  Two correct plans differ by fp32
-# summation order only (measured over every entry of the shipped database: profiles/r4_plan_replay.json); a mis-tiled edge, a
-# wrong split reduce or a stale workspace is orders of magnitude above that and must not ship because it is fast.
-TUNE_AGREE = {"conv": 2e-5, "wgrad": 2e-4, "wino4": 2e-5}   # wino4: the F(4x4, 3x3) Winograd kernel (round 5 points 0, +-3/4, +-5/4: 0.4e-6 .. 5e-6 of
-#                                                              the output scale against float64, tests/test_gpu_wino.py; 6e-5 with round 4's 0, +-1, +-2)
-TUNE_REJECTED = []   # (key, algo, measured disagreement) of every candidate refused
-TUNE_SKIPPED = []    # keys whose tuning was put off because the call's result was all zero (no scale to compare candidates against)
-TUNE_ZERO_RETRIES = 3   # ... at most this often per key; then the built-in plan is cached for it
-_tune_zero_seen = {}
+def _conv_trial(lib, d, ios, G: int, device, colsum: bool, trial_out):
+    """-> (run, result, reset, penalty) of tune.autotune for the conv launch d / ios.  Trials run in `trial_out` (conv2d_raw's output, which
+    the launch writes afterwards), else on scratch outputs with the same strides: timing runs would accumulate into live data, and the tuner
+    compares every candidate's result with the baseline plan's on a tensor it owns (tune.scratch: its pattern is from torch's generator)."""
+    if trial_out is not None:
+        tio, res_t, reset = ios, trial_out, None
+    else:
+        span = (d.N * d.OH * d.OW - 1) * d.ldy + d.OC
+        res_t, reset = tune.scratch(G * span + 64, device)
+        tio = (L.ConvIO * G)()
+        C.memmove(tio, ios, C.sizeof(tio))
+        for g in range(G):
+            tio[g].y = res_t.data_ptr() + 4 * g * span
+            if ios[g].pre == ios[g].y:
+                tio[g].pre = tio[g].y
+            if ios[g].res == ios[g].y:
+                tio[g].res = tio[g].y
+    keep, cost = [], 0.0
+
+    def run(a):
+        nonlocal cost
+        d.reserved = a
+        if colsum:   # (the layout of the partial rows depends on the plan)
+            try:
+                _, _, nf = _colsum_layout(lib, d, G)
+            except L.CrdrHipError:
+                return False
+            keep[:] = [torch.empty(G * nf, dtype=torch.float32, device=device)]
+            for g in range(G):
+                tio[g].cs = keep[0].data_ptr() + 4 * g * nf
+        ok, cost = _tune_conv_launch(lib, d, tio, G, device)
+        return ok
+    return run, (lambda: res_t), reset, (lambda: cost)
 
 
-def _autotune(key, ncfg: int, max_log2_split: int, run, extra=(), penalty=None, result=None, reset=None, agree: float = 2e-5) -> int:
-    """run(algo) -> bool (False if the library rejects the combination). Returns the fastest algo id.  penalty() -> ms added to
-    the candidate just timed: cost the launch causes elsewhere (the batched reduce reads every partial slab a weight-gradient
-    launch writes, so a deeper pixel split that is 1 % faster in isolation can cost more than it gains).
-    result() -> the tensor the launch just wrote (for weight-gradient slab launches: after their reduce); reset() restores the
-    operands a launch reads AND writes (accumulating epilogues) before a run whose result is compared."""
-    def fresh(a):
-        if reset is not None:
-            reset()
-        return run(a)
-    if torch.cuda.is_current_stream_capturing():
-        return 0   # timing needs host syncs: a key first seen under capture runs the built-in plan (and is tuned by a later eager call)
-    fresh(0)
-    ref = result().detach().clone() if result is not None else None
-    ref_scale = float(ref.abs().max()) if ref is not None else 0.0
-    if ref is not None and not ref_scale > 1e-30:
-        # the operands of this call happen to give an all-zero (or denormal) result -- a zero gradient at warm-up, a masked branch: nothing
-        # can be compared against it, and caching the baseline plan for the key would silently de-tune it.  Keep the built-in plan for THIS
-        # call only; the next call with the same key tunes on its own operands.
-        TUNE_SKIPPED.append(key)
-        _tune_zero_seen[key] = _tune_zero_seen.get(key, 0) + 1
-        if _tune_zero_seen[key] >= TUNE_ZERO_RETRIES:   # persistently zero (a masked branch, a zero-initialised layer): stop paying a launch, a clone and
-            _algo_cache[key] = 0                        # a host sync per call -- the built-in plan is cached and reported
-            TUNE_LOG.append((key, 0, 0.0, 0.0))
-        return 0
-    best, best_t = 0, _time_call(lambda: run(0)) + (penalty() if penalty else 0.0)
-    base_t = best_t
-    cands = [tile_id(c, ls) for c in range(ncfg) for ls in range(max_log2_split + 1)] + list(extra)
-    for algo in cands:
-        try:
-            if not fresh(algo):
-                continue
-            if ref is not None:
-                dis = float((result() - ref).abs().max())
-                tol = TUNE_AGREE["wino4"] if ((algo & 0xff) == _ids().wino4 and key[0] in ("c", "g", "m")) else agree
-                if not dis <= tol * ref_scale:   # (NaN fails too)
-                    TUNE_REJECTED.append((key, algo, dis / (ref_scale + 1e-30)))
-                    continue
-            t = _time_call(lambda: run(algo)) + (penalty() if penalty else 0.0)
-        except L.CrdrHipError:
-            continue
-        if t < best_t:
-            best, best_t = algo, t
-    _algo_cache[key] = best
-    TUNE_LOG.append((key, best, base_t, best_t))
-    return best
+def _wgrad_trial(lib, d, G: int, pa, qa, device, whole: bool):
+    """-> (run, result, reset, penalty) of tune.autotune for the weight gradients d / pa / qa, written to a tensor of the trial's own: the complete
+    gradient with accumulate = 0 (`whole`; on a copy of d, the caller's keeps its accumulate), or the slab launch and the batched reduce of a deferred one."""
+    gsize = d.gI * d.gJ * d.kh * d.kw
+    tmp = torch.zeros(G * gsize + 64, dtype=torch.float32, device=device)
+    ta = (C.c_void_p * G)(*[tmp.data_ptr() + 4 * g * gsize for g in range(G)])
+    jobs_t = (L.WgradJob * G)()
+    d, slab = L.WgradDesc.from_buffer_copy(d), 0
+    d.accumulate = 0 if whole else d.accumulate
 
+    def run(a):
+        nonlocal slab
+        d.algo = _wa(a)
+        nb = lib.crdr_conv2d_wgrad_grouped_workspace(C.byref(d), G)
+        if nb == 0 or nb > (2 << 30):
+            return False
+        slab = nb
+        w_, wn_ = workspace(nb, device)
+        if whole:
+            return lib.crdr_conv2d_wgrad(C.byref(d), pa[0], qa[0], ta[0], w_, wn_, _stream()) == 0
+        return lib.crdr_conv2d_wgrad_partial_grouped(C.byref(d), pa, qa, ta, G, w_, wn_, jobs_t, _stream()) == 0
+    if whole:
+        return run, (lambda: tmp), None, None
 
-def _tune_scratch(nfloats: int, device):
-    """-> (scratch output tensor for tuner trials, reset() that restores its fixed pseudo-random content: accumulating epilogues
-    read what they write, and a result is only comparable between plans if both started from the same content)"""
-    scratch = torch.empty(nfloats, dtype=torch.float32, device=device)
-    pattern = torch.rand(nfloats, dtype=torch.float32, device=device) - 0.5
-    return scratch, (lambda: scratch.copy_(pattern))
-
-
-DEFAULT_TUNE_DB = os.path.join(os.path.dirname(__file__), "tune_gfx950.json")
-
-
-def _tune_signature() -> str:
-    lib = L.load()
-    return (f"v{lib.crdr_version()}-c{lib.crdr_conv2d_num_configs()}-s{lib.crdr_conv2d_num_stream_configs()}"
-            f"-w{lib.crdr_conv2d_wgrad_num_configs()}+{lib.crdr_conv2d_wgrad_num_wino_configs() - 1}-n{lib.crdr_conv2d_num_wino_configs()}")
-
-
-def save_tune_cache(path: str) -> None:
-    """Persist the autotuner's choices (a perf database in the MIOpen sense): {repr(shape key): algo id}."""
-    import json
-    with open(path, "w") as f:
-        json.dump({"signature": _tune_signature(), "algos": {repr(k): v for k, v in _algo_cache.items()}}, f, indent=0)
-
-
-def load_tune_cache(path: str, only_kinds=None, ignore_signature: bool = False, skip=None) -> int:
-    """Load choices saved by save_tune_cache; ignored (returns 0) if the library's configuration list has changed.
-    only_kinds / ignore_signature: seed a rebuild of the database with the entries of kernel families that did not change
-    (key[0]: "c" / "g" / "m" conv launches, "w" / "wm" weight gradients)."""
-    import ast
-    import json
-    if not os.path.exists(path):
-        return 0
-    with open(path) as f:
-        db = json.load(f)
-    if db.get("signature") != _tune_signature() and not ignore_signature:
-        return 0
-    n = 0
-    for k, v in db["algos"].items():
-        key = ast.literal_eval(k)
-        if only_kinds is not None and key[0] not in only_kinds:
-            continue
-        if skip is not None and skip(key):   # (entries the caller wants timed again, e.g. shapes a new kernel applies to)
-            continue
-        _algo_cache.setdefault(key, int(v))
-        n += 1
-    return n
+    def result():   # the trial's slabs reduced into tmp (the jobs accumulate: tmp is zeroed by reset())
+        reduce_jobs_now(jobs_t, device)
+        return tmp
+    # + the batched reduce's read of these slabs at its measured 3.8 TB/s (profiles/r2_h_hbm_families.json)
+    return run, result, tmp.zero_, (lambda: slab / 3.8e9)
 
 
 # Optional per-launch timing (bench.py): {"igemm": [(flops, ev0, ev1), ...], "wgrad": [...]} or None.
@@ -357,24 +251,30 @@ def _prof_end(kind: str, flops: float, e0, label: str = "", nbytes: float = 0.0)
 _WS_HEAD = 4 * 16384  # bytes at the head of every scratch buffer: the split-K tickets of the conv kernels (CRDR_CONV_TICKETS int32)
 
 
+def _ws_fit(key, device, need: Optional[int]) -> torch.Tensor:
+    """-> the scratch buffer of `key` with at least `need` bytes (None, reserve_workspace: as many as a new buffer gets).  A new buffer is zeroed
+    and sized for the largest request seen so far plus headroom, the one it supersedes stays alive; a launch's request may not grow under capture."""
+    size = max(int(_ws_max * 1.25), 1 << 20)
+    buf = _ws_cache.get(key)
+    if buf is None or buf.numel() < (size if need is None else need):
+        if need is not None and torch.cuda.is_current_stream_capturing():
+            # a buffer born inside a capture would belong to that graph's private pool and die with it
+            raise L.CrdrHipError("workspace must be reserved before graph capture (ops.reserve_workspace); "
+                                 f"need {need} bytes, have {0 if buf is None else buf.numel()}")
+        if buf is not None:
+            _ws_keep.append(buf)
+        buf = _ws_cache[key] = torch.zeros(size, dtype=torch.uint8, device=device)
+    return buf
+
+
 def workspace(nbytes: int, device, conv: bool = False) -> Tuple[int, int]:
     """Grow-only per-device scratch (kernels on one stream serialise, so one buffer is enough).  The buffer is born zeroed and
     its first _WS_HEAD bytes belong to the conv kernels' split-K tickets, which every launch leaves at zero (include/crdr_hip.h,
     CRDR_CONV_TICKETS): conv launches (`conv=True`) get the buffer from its start, everything else the part behind the head."""
     global _ws_max
-    key = (device.index if device.index is not None else torch.cuda.current_device(), _stream())
     nbytes = int(nbytes) + (0 if conv else _WS_HEAD)
     _ws_max = max(_ws_max, nbytes)
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        if torch.cuda.is_current_stream_capturing():
-            # a buffer born inside a capture would belong to that graph's private pool and die with it
-            raise L.CrdrHipError("workspace must be reserved before graph capture (ops.reserve_workspace); "
-                                 f"need {nbytes} bytes, have {0 if buf is None else buf.numel()}")
-        if buf is not None:
-            _ws_keep.append(buf)
-        buf = torch.zeros(max(int(_ws_max * 1.25), 1 << 20), dtype=torch.uint8, device=device)
-        _ws_cache[key] = buf
+    buf = _ws_fit((device.index if device.index is not None else torch.cuda.current_device(), _stream()), device, nbytes)
     if conv:
         return buf.data_ptr(), buf.numel()
     return buf.data_ptr() + _WS_HEAD, buf.numel() - _WS_HEAD
@@ -384,13 +284,7 @@ def reserve_workspace(device, stream: "torch.cuda.Stream") -> None:
     """Give `stream` its scratch buffer from the ordinary allocator, sized for the largest request seen so far
     (eager warm-up).  Call before capturing a graph on that stream."""
     dev = torch.device(device)
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream.cuda_stream)
-    buf = _ws_cache.get(key)
-    need = max(int(_ws_max * 1.25), 1 << 20)
-    if buf is None or buf.numel() < need:
-        if buf is not None:
-            _ws_keep.append(buf)
-        _ws_cache[key] = torch.zeros(need, dtype=torch.uint8, device=dev)
+    _ws_fit((dev.index if dev.index is not None else torch.cuda.current_device(), stream.cuda_stream), dev, None)
 
 
 def _pixel_stride(t: torch.Tensor) -> int:
@@ -499,46 +393,18 @@ def _conv(lib, d, ios, G: int, key, device, *, flops: float, label: str, nbytes:
     The plan: an explicit id (`algo`, else FORCED_CONV_ALGO), else the Winograd kernel PREFER_WINOGRAD asks for, else the tuned plan of
     `key` (AUTOTUNE; None: this launch is never tuned), else the plan the library would give a launch of `plan_as` problems, else the
     built-in plan.  colsum: the launch carries CRDR_EPI_COLSUM; -> [(partial-row address, rows, ld)] per problem, in colsum_queue(device)'s
-    arena (None without colsum).  trial_out: conv2d_raw's output, which its tuner trials run in (the launch writes it afterwards) -- the
-    scratch outputs of the other launches draw their pattern from torch's generator."""
+    arena (None without colsum).  trial_out: conv2d_raw's output, which its tuner trials run in (_conv_trial)."""
     forced = algo or FORCED_CONV_ALGO
     wino = 0 if forced else _prefer_wino(d, G)
     GP = plan_as or G
     if forced or wino:
         d.reserved = forced or wino
-    elif AUTOTUNE and key is not None and (GP == G or key in _algo_cache):
-        algo = _algo_cache.get(key)
+    elif AUTOTUNE and key is not None and (GP == G or key in tune.algo_cache):
+        algo = tune.algo_cache.get(key)
         if algo is None:
-            if trial_out is not None:
-                tio, res_t, reset = ios, trial_out, None
-            else:
-                # trials run on scratch outputs with the same strides (timing runs would accumulate into live data; and the tuner
-                # compares every candidate's result with the baseline plan's on a tensor it owns)
-                span = (d.N * d.OH * d.OW - 1) * d.ldy + d.OC
-                res_t, reset = _tune_scratch(G * span + 64, device)
-                tio = (L.ConvIO * G)()
-                C.memmove(tio, ios, C.sizeof(tio))
-                for g in range(G):
-                    tio[g].y = res_t.data_ptr() + 4 * g * span
-                    if ios[g].pre == ios[g].y:
-                        tio[g].pre = tio[g].y
-                    if ios[g].res == ios[g].y:
-                        tio[g].res = tio[g].y
-            keep = []
-
-            def run(a):
-                d.reserved = a
-                if colsum:   # (the layout of the partial rows depends on the plan)
-                    try:
-                        _, _, nf = _colsum_layout(lib, d, G)
-                    except L.CrdrHipError:
-                        return False
-                    keep[:] = [torch.empty(G * nf, dtype=torch.float32, device=device)]
-                    for g in range(G):
-                        tio[g].cs = keep[0].data_ptr() + 4 * g * nf
-                return _tune_conv_launch(lib, d, tio, G, device)
-            algo = _autotune(key, lib.crdr_conv2d_num_configs(), 4, run, extra=_stream_ids(), result=lambda: res_t, reset=reset,
-                             agree=TUNE_AGREE["conv"], penalty=lambda: _tune_w4_penalty[0])
+            run, result, reset, penalty = _conv_trial(lib, d, ios, G, device, colsum, trial_out)
+            algo = tune.autotune(key, lib.crdr_conv2d_num_configs(), 4, run, extra=_stream_ids(), result=result, reset=reset,
+                                 agree=tune.AGREE["conv"], penalty=penalty)
         d.reserved = algo
     elif GP != G:
         d.reserved = lib.crdr_conv2d_choose_algo(C.byref(d), GP)
@@ -560,45 +426,18 @@ def _conv(lib, d, ios, G: int, key, device, *, flops: float, label: str, nbytes:
 def _wgrad(lib, d, G: int, ps, qs, gs, key, device, *, flops: float, label: str, whole: bool = False, algo: int = 0,
            defer: bool = True) -> list:
     """Plan and launch the G weight gradients that d describes (operand / gradient addresses ps, qs, gs), and record their profile entry.
-    The plan: the explicit `algo`, else the tuned plan of `key` (AUTOTUNE), else the built-in plan.  A tuner trial runs the complete weight
-    gradient with accumulate = 0 (`whole`), or the slab launch and the batched reduce that a deferred launch takes.  The slabs' reduction
-    is deferred onto WGRAD_DEFER (defer=False: reduced inside the same call); -> the jobs queued there, for the caller to adjust."""
+    The plan: the explicit `algo`, else the tuned plan of `key` (AUTOTUNE), else the built-in plan.  whole: a tuner trial runs the complete
+    weight gradient, not the slab launch (_wgrad_trial).  The slabs' reduction is deferred onto WGRAD_DEFER (defer=False: reduced inside the
+    same call); -> the jobs queued there, for the caller to adjust."""
     pa, qa, ga = ((C.c_void_p * G)(*v) for v in (ps, qs, gs))
     if algo:
         d.algo = _wa(algo)
     elif AUTOTUNE:
-        algo = _algo_cache.get(key)
+        algo = tune.algo_cache.get(key)
         if algo is None:
-            gsize = d.gI * d.gJ * d.kh * d.kw
-            tmp = torch.zeros(G * gsize + 64, dtype=torch.float32, device=device)
-            ta = (C.c_void_p * G)(*[tmp.data_ptr() + 4 * g * gsize for g in range(G)])
-            jobs_t = (L.WgradJob * G)()
-            slab = [0]
-            accumulate = d.accumulate
-            if whole:
-                d.accumulate = 0
-
-            def run(a):
-                d.algo = _wa(a)
-                nb = lib.crdr_conv2d_wgrad_grouped_workspace(C.byref(d), G)
-                if nb == 0 or nb > (2 << 30):
-                    return False
-                slab[0] = nb
-                w_, wn_ = workspace(nb, device)
-                if whole:
-                    return lib.crdr_conv2d_wgrad(C.byref(d), pa[0], qa[0], ta[0], w_, wn_, _stream()) == 0
-                return lib.crdr_conv2d_wgrad_partial_grouped(C.byref(d), pa, qa, ta, G, w_, wn_, jobs_t, _stream()) == 0
-            if whole:
-                result, reset, penalty = (lambda: tmp), None, None
-            else:
-                def result():   # the trial's slabs reduced into tmp (the jobs accumulate: tmp is zeroed by reset())
-                    reduce_jobs_now(jobs_t, device)
-                    return tmp
-                # + the batched reduce's read of these slabs at its measured 3.8 TB/s (profiles/r2_h_hbm_families.json)
-                reset, penalty = tmp.zero_, (lambda: slab[0] / 3.8e9)
-            algo = _autotune(key, lib.crdr_conv2d_wgrad_num_configs(), 8, run, extra=_wgrad_wino4_ids(), penalty=penalty, result=result,
-                             reset=reset, agree=TUNE_AGREE["wgrad"])
-            d.accumulate = accumulate
+            run, result, reset, penalty = _wgrad_trial(lib, d, G, pa, qa, device, whole)
+            algo = tune.autotune(key, lib.crdr_conv2d_wgrad_num_configs(), 8, run, extra=_wgrad_wino4_ids(), penalty=penalty, result=result,
+                                 reset=reset, agree=tune.AGREE["wgrad"])
         d.algo = _wa(algo)
     nbytes = lib.crdr_conv2d_wgrad_grouped_workspace(C.byref(d), G)
     e0 = _prof_begin()

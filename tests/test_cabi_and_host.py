@@ -322,9 +322,9 @@ def test_shipped_perf_database_matches_the_library():
     also be ids this library knows."""
     import json
     from crdr_amd.hip import lib as L
-    from crdr_amd.hip import ops
-    db = json.load(open(ops.DEFAULT_TUNE_DB))
-    assert db["signature"] == ops._tune_signature(), (db["signature"], ops._tune_signature())
+    from crdr_amd.hip import tune
+    db = json.load(open(tune.DEFAULT_DB))
+    assert db["signature"] == tune.signature(), (db["signature"], tune.signature())
     lib = L.load()
     nconv = lib.crdr_conv2d_num_configs() + lib.crdr_conv2d_num_stream_configs() + lib.crdr_conv2d_num_wino_configs()
     nw = lib.crdr_conv2d_wgrad_num_configs() + lib.crdr_conv2d_wgrad_num_wino_configs() - 1   # (the F(3x3, 4x4) slab kernel: the id behind the last configuration)

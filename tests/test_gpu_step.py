@@ -274,7 +274,7 @@ class _ShippedPlans:
         return self
 
     def tuned_here(self):
-        """shapes the database did not hold (tuned on the spot, with the agreement check of ops._autotune)"""
+        """shapes the database did not hold (tuned on the spot, with the agreement check of tune.autotune)"""
         return [k for k, *_ in self.ops.TUNE_LOG[self.log0:]]
 
     def __exit__(self, *exc):

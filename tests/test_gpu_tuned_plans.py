@@ -65,25 +65,25 @@ class _Replay:
     """AUTOTUNE on with the shipped database and the tuner disarmed / AUTOTUNE off (built-in plan)."""
 
     def __enter__(self):
-        from crdr_amd.hip import ops
-        self.ops = ops
-        self.keep = (ops.AUTOTUNE, dict(ops._algo_cache), ops._autotune, ops.MATRIX_BF16X3, ops.WGRAD_DEFER)
+        from crdr_amd.hip import ops, tune
+        self.ops, self.tune = ops, tune
+        self.keep = (ops.AUTOTUNE, dict(tune.algo_cache), tune.autotune, ops.MATRIX_BF16X3, ops.WGRAD_DEFER)
         self.keep6 = ops.MATRIX_BF16X6
-        ops._algo_cache.clear()
-        assert ops.load_tune_cache(DB) > 0, "the shipped perf database is not of this library build (signature mismatch)"
+        tune.algo_cache.clear()
+        assert tune.load(DB) > 0, "the shipped perf database is not of this library build (signature mismatch)"
 
         def refuse(key, *a, **k):
             raise AssertionError(f"replay reconstructed a key the shipped database does not hold: {key}")
-        ops._autotune = refuse
+        tune.autotune = refuse
         ops.WGRAD_DEFER = ops.DeferredWgrad(_dev(), arena_bytes=1 << 30)
         return self
 
     def __exit__(self, *exc):
-        ops = self.ops
-        ops.AUTOTUNE, cache, ops._autotune, ops.MATRIX_BF16X3, ops.WGRAD_DEFER = self.keep
+        ops, tune = self.ops, self.tune
+        ops.AUTOTUNE, cache, tune.autotune, ops.MATRIX_BF16X3, ops.WGRAD_DEFER = self.keep
         ops.MATRIX_BF16X6 = self.keep6
-        ops._algo_cache.clear()
-        ops._algo_cache.update(cache)
+        tune.algo_cache.clear()
+        tune.algo_cache.update(cache)
 
     def mode(self, tuned: bool, prec: int):
         """prec: 0 exact fp32, 3 / 6 the split-bf16 modes the entry was tuned in"""
@@ -509,9 +509,9 @@ def test_every_tuned_wgrad_plan_matches_builtin_and_float64(kind):
 
 
 def test_autotuner_rejects_a_candidate_that_disagrees():
-    """ops._autotune compares every candidate's output with the baseline plan's before it may win (a mis-tiled edge must not ship
+    """tune.autotune compares every candidate's output with the baseline plan's before it may win (a mis-tiled edge must not ship
     because it is fast): a `run` whose candidate 2 writes a wrong value is never chosen, whatever its time."""
-    from crdr_amd.hip import ops
+    from crdr_amd.hip import tune
     dev = _dev()
     out = torch.zeros(4096, device=dev)
     slow = torch.zeros(1 << 24, device=dev)
@@ -525,11 +525,116 @@ def test_autotuner_rejects_a_candidate_that_disagrees():
         if a == 3:
             slow[:1 << 20].add_(1.0)
         return a in (0, 2, 3)
-    keep = dict(ops._algo_cache)
+    keep = dict(tune.algo_cache)
     try:
-        best = ops._autotune(("test-reject",), 3, 0, run, result=lambda: out)
+        best = tune.autotune(("test-reject",), 3, 0, run, result=lambda: out)
     finally:
-        ops._algo_cache.clear()
-        ops._algo_cache.update(keep)
+        tune.algo_cache.clear()
+        tune.algo_cache.update(keep)
     assert best == 3, best
-    assert any(k == ("test-reject",) and a == 2 for k, a, _ in ops.TUNE_REJECTED)
+    assert any(k == ("test-reject",) and a == 2 for k, a, _ in tune.REJECTED)
+
+
+def _tuned_then_forced(kind, launch):
+    """launch(None) with AUTOTUNE on and an empty cache tunes its key on the spot; -> (key, chosen id) after comparing what it left in the live
+    tensors, bit for bit, with launch(chosen id) on fresh copies of the same operands, during which the tuner may not run again"""
+    from crdr_amd.hip import ops, tune
+    keep = (ops.AUTOTUNE, ops.FORCED_CONV_ALGO, ops.PREFER_WINOGRAD, ops.WGRAD_DEFER, tune.autotune, dict(tune.algo_cache))
+    try:
+        ops.AUTOTUNE, ops.FORCED_CONV_ALGO, ops.PREFER_WINOGRAD = True, 0, False
+        tune.algo_cache.clear()
+        log0 = len(tune.LOG)
+        live = launch(None)
+        assert len(tune.algo_cache) == 1, list(tune.algo_cache)
+        (key, algo), = tune.algo_cache.items()
+        assert key[0] == kind, key
+        assert [k for k, *_ in tune.LOG[log0:]] == [key], tune.LOG[log0:]
+
+        def refuse(k, *a, **kw):
+            raise AssertionError(f"the forced run tuned again: {k}")
+        tune.autotune = refuse
+        forced = launch(algo)
+    finally:
+        ops.AUTOTUNE, ops.FORCED_CONV_ALGO, ops.PREFER_WINOGRAD, ops.WGRAD_DEFER, tune.autotune, cache = keep
+        tune.algo_cache.clear()
+        tune.algo_cache.update(cache)
+    assert len(live) == len(forced)
+    for i, (a, b) in enumerate(zip(live, forced)):   # the trials neither wrote into nor accumulated onto live data
+        assert torch.equal(a, b), f"{key}: result {i} differs from the run with id {algo} forced by {float((a - b).abs().max()):.3e}"
+    return key, algo
+
+
+# The trial builders (ops._conv_trial / ops._wgrad_trial) are reached only when a key misses the database.  N = 1, 8 x 8 pixels, 32 -> 32
+# channels, 3 x 3 stride 1 pad 1: the smallest shape on which tiled, split, streaming-refused and Winograd candidates all get planned or refused.
+_TN, _TH, _TC, _TK = 1, 8, 32, (3, 3)
+
+
+def test_tuner_trials_conv2d_raw_run_in_the_live_output():
+    from crdr_amd.hip import lib as L, ops
+    x, y0, b = _rand((_TN, _TH, _TH, _TC), 1), _rand((_TN, _TH, _TH, _TC), 2), _rand((_TC,), 3)
+    wp = ops.pack_weight(_rand((_TC, _TC, 3, 3), 4, (_TC * 9) ** -0.5), transpose=False)
+
+    def launch(algo):
+        y = y0.clone()
+        ops.conv2d_raw(_nchw(x, _TC), wp, _TC, _TK, 1, 1, False, (_TH, _TH), bias=b, flags=L.EPI_BIAS, out=_nchw(y, _TC), algo=algo or 0)
+        torch.cuda.synchronize()
+        return [y]
+    _tuned_then_forced("c", launch)
+
+
+def test_tuner_trials_conv_multi_run_on_scratch_outputs_and_colsum_rows():
+    """G = 2 with the outputs as their own residual operands (the trials remap them to the scratch) and CRDR_EPI_COLSUM (partial rows per plan)"""
+    from crdr_amd.hip import ops
+    dev = _dev()
+    xs = [_rand((_TN, _TH, _TH, _TC), 10 + g) for g in range(2)]
+    y0 = [_rand((_TN, _TH, _TH, _TC), 20 + g) for g in range(2)]
+    wps = [ops.pack_weight(_rand((_TC, _TC, 3, 3), 30 + g, (_TC * 9) ** -0.5), transpose=False) for g in range(2)]
+
+    def launch(algo):
+        ops.FORCED_CONV_ALGO = algo or 0
+        ys = [t.clone() for t in y0]
+        sums = [torch.zeros(2, _TC, device=dev) for _ in range(2)]
+        yv = [ops.view(t, 0, _TC) for t in ys]
+        q = ops.colsum_queue(dev)
+        cs = ops.conv_multi(_TN, _TH, _TH, _TH, _TH, [ops.view(t, 0, _TC) for t in xs], [t.data_ptr() for t in wps], yv, _TC, _TK, 1, 1, False,
+                            wrows=wps[0].shape[1], wcols=wps[0].shape[2], ress=yv, colsum=True, device=dev)
+        for (ptr, rows, ld), s in zip(cs, sums):
+            q.add(ptr, rows, ld, _TC, s[0].data_ptr(), s[1].data_ptr(), False)
+        q.flush(("tuner-trials", algo is None))
+        torch.cuda.synchronize()
+        return ys + sums
+    _tuned_then_forced("m", launch)
+
+
+def test_tuner_trials_wgrad_raw_keep_accumulate():
+    """the complete weight gradient (`whole`) with accumulate=True into a pre-filled g: the trials run with accumulate = 0 on a tensor of their own"""
+    from crdr_amd.hip import ops
+    p, q, g0 = _rand((_TN, _TH, _TH, _TC), 40), _rand((_TN, _TH, _TH, _TC), 41), _rand((_TC, _TC, 3, 3), 42)
+
+    def launch(algo):
+        ops.WGRAD_DEFER = None
+        g = g0.clone()
+        ops.conv2d_wgrad_raw(_nchw(p, _TC), _nchw(q, _TC), g, _TK, 1, 1, accumulate=True, algo=algo or 0)
+        torch.cuda.synchronize()
+        return [g]
+    _tuned_then_forced("w", launch)
+
+
+def test_tuner_trials_wgrad_group_slabs_and_reduce():
+    """G = 2 slab launches under a DeferredWgrad: a trial is the slab launch plus ops.reduce_jobs_now.  wgrad_group takes no id: the forced run
+    finds the chosen one under its key, with the tuner refusing to run"""
+    from crdr_amd.hip import ops
+    dev = _dev()
+    ps = [_rand((_TN, _TH, _TH, _TC), 50 + g) for g in range(2)]
+    qs = [_rand((_TN, _TH, _TH, _TC), 60 + g) for g in range(2)]
+    g0 = [_rand((_TC, _TC, 3, 3), 70 + g) for g in range(2)]
+
+    def launch(algo):
+        ops.WGRAD_DEFER = ops.DeferredWgrad(dev, arena_bytes=1 << 26)
+        gs = [t.clone() for t in g0]
+        ops.wgrad_group(_TN, _TH, _TH, [ops.view(t, 0, _TC) for t in ps], [ops.view(t, 0, _TC) for t in qs], [(g.data_ptr(), _TC) for g in gs],
+                        _TC, _TC, _TK, 1, device=dev)
+        ops.flush_wgrads(("tuner-trials", algo is None))
+        torch.cuda.synchronize()
+        return gs
+    _tuned_then_forced("wg", launch)

@@ -484,7 +484,7 @@ def test_winograd_f4x4_tuned_plan_demoted_on_misaligned_output():
     """a tuned F(4x4) plan is keyed by shape and strides, not by pointer alignment: a launch whose output view starts at a channel offset that
     is not a multiple of 4 floats (the kernel's epilogue works with 16-byte accesses) runs the built-in plan instead, bit for bit"""
     from crdr_amd.hip import lib as L
-    from crdr_amd.hip import ops
+    from crdr_amd.hip import ops, tune
     dev = _dev()
     n, ci, h, w, co = 2, 64, 20, 72, 96
     x = _rand(n, ci, h, w, seed=5).to(dev).contiguous(memory_format=torch.channels_last)
@@ -501,19 +501,19 @@ def test_winograd_f4x4_tuned_plan_demoted_on_misaligned_output():
 
     def refuse(k, *a, **kw):
         raise AssertionError(f"the launch missed its preloaded tuner key: {k}")
-    keep = (ops.AUTOTUNE, dict(ops._algo_cache), ops._autotune)
+    keep = (ops.AUTOTUNE, dict(tune.algo_cache), tune.autotune)
     try:
         ops.AUTOTUNE = False
         builtin = run()
-        ops.AUTOTUNE, ops._autotune = True, refuse
-        ops._algo_cache[key] = _wino_id() + 2
+        ops.AUTOTUNE, tune.autotune = True, refuse
+        tune.algo_cache[key] = _wino_id() + 2
         before = ops.WINO4_DEMOTED[0]
         demoted = run()
         assert ops.WINO4_DEMOTED[0] == before + 1
     finally:
-        ops.AUTOTUNE, ops._autotune = keep[0], keep[2]
-        ops._algo_cache.clear()
-        ops._algo_cache.update(keep[1])
+        ops.AUTOTUNE, tune.autotune = keep[0], keep[2]
+        tune.algo_cache.clear()
+        tune.algo_cache.update(keep[1])
     assert torch.equal(demoted, builtin)
 
 

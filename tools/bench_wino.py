@@ -7,7 +7,7 @@ import torch
 
 sys.path.insert(0, ".")
 from crdr_amd.hip import lib as L  # noqa: E402
-from crdr_amd.hip import ops  # noqa: E402
+from crdr_amd.hip import ops, tune  # noqa: E402
 
 SHAPES = [(128, 128, 128), (96, 96, 128), (64, 128, 128), (128, 64, 128), (128, 128, 64), (96, 96, 64), (128, 256, 64), (256, 128, 64),
           (256, 512, 32), (512, 256, 32), (128, 128, 32), (96, 96, 32), (160, 160, 16), (320, 320, 16)]
@@ -23,8 +23,8 @@ def main():
     ap.add_argument("--k5s2", action="store_true", help="the 5x5 stride-2 conv / transposed conv shapes: tuned direct kernel vs F(4x4, 3x3) over parity sub-filters / output phases")
     ap.add_argument("--wgrad", action="store_true", help="time the weight-gradient kernels instead (direct slab kernel vs Winograd F(3x3, 2x2))")
     a = ap.parse_args()
-    ops.TUNE_COLD = a.cold
-    ops.TUNE_ROUNDS = 3
+    tune.COLD = a.cold
+    tune.ROUNDS = 3
     lib = L.load()
     wid = lib.crdr_conv2d_num_configs() + 1 + lib.crdr_conv2d_num_stream_configs()
     dev = torch.device("cuda:0")
@@ -42,7 +42,7 @@ def main():
                 for cfg in cfgs:
                     for ls in range(9):
                         try:
-                            t = ops._time_call(lambda: ops.conv2d_wgrad_raw(dy, x, g, (3, 3), 1, 1, False, algo=(cfg + 1) | (ls << 8), defer=False), reps=3)
+                            t = tune.time_call(lambda: ops.conv2d_wgrad_raw(dy, x, g, (3, 3), 1, 1, False, algo=(cfg + 1) | (ls << 8), defer=False), reps=3)
                         except (L.CrdrHipError, AssertionError):
                             continue
                         best = min(best, (t, cfg, ls))
@@ -63,14 +63,14 @@ def main():
             best = (1e9, 0)
             for cfg in range(lib.crdr_conv2d_num_configs()):
                 try:
-                    t = ops._time_call(lambda: ops.conv2d_raw(x, wp, co, (5, 5), 2, 2, bool(tr), out, bias=b, flags=1, algo=cfg + 1), reps=3)
+                    t = tune.time_call(lambda: ops.conv2d_raw(x, wp, co, (5, 5), 2, 2, bool(tr), out, bias=b, flags=1, algo=cfg + 1), reps=3)
                 except L.CrdrHipError:
                     continue
                 best = min(best, (t, cfg))
             y0 = ops.conv2d_raw(x, wp, co, (5, 5), 2, 2, bool(tr), out, bias=b, flags=1, algo=best[1] + 1)
             y4 = ops.conv2d_raw(x, wp, co, (5, 5), 2, 2, bool(tr), out, bias=b, flags=1, algo=wid + 2)
             err = float((y4 - y0).abs().max() / y0.abs().max())
-            t4 = ops._time_call(lambda: ops.conv2d_raw(x, wp, co, (5, 5), 2, 2, bool(tr), out, bias=b, flags=1, algo=wid + 2), reps=3)
+            t4 = tune.time_call(lambda: ops.conv2d_raw(x, wp, co, (5, 5), 2, 2, bool(tr), out, bias=b, flags=1, algo=wid + 2), reps=3)
             fl = 2.0 * a.bs * (hw * hw if tr else out[0] * out[1]) * ci * co * 25
             print(f"{'T' if tr else 'C'} {ci:4d}->{co:4d} k5s2 in{hw:3d}: direct {best[0] * 1e3:8.1f} us ({fl / best[0] / 1e9:6.1f} TF, cfg {best[1]})   F(4x4) {t4 * 1e3:8.1f} us "
                   f"({fl / t4 / 1e9:6.1f} TF-eq) x{best[0] / t4:.2f}   max rel diff {err:.2e}", flush=True)
@@ -84,17 +84,17 @@ def main():
         best = (1e9, 0)
         for cfg in range(0 if a.wino_only else lib.crdr_conv2d_num_configs()):
             try:
-                t = min(ops._time_call(lambda: ops.conv2d_raw(x, wp, co, (kk, kk), 1, kk // 2, False, (hw, hw), bias=b, flags=3, algo=(cfg + 1) | (ls << 8)), reps=3)
+                t = min(tune.time_call(lambda: ops.conv2d_raw(x, wp, co, (kk, kk), 1, kk // 2, False, (hw, hw), bias=b, flags=3, algo=(cfg + 1) | (ls << 8)), reps=3)
                         for ls in (range(3) if a.k5 else range(1)))
             except L.CrdrHipError:
                 continue
             best = min(best, (t, cfg))
-        tw = ops._time_call(lambda: ops.conv2d_raw(x, wp, co, (kk, kk), 1, kk // 2, False, (hw, hw), bias=b, flags=3, algo=wid), reps=3)
+        tw = tune.time_call(lambda: ops.conv2d_raw(x, wp, co, (kk, kk), 1, kk // 2, False, (hw, hw), bias=b, flags=3, algo=wid), reps=3)
         fl = 2.0 * a.bs * hw * hw * ci * co * kk * kk
         t4 = None
         if lib.crdr_conv2d_num_wino_configs() > 2:
             try:   # F(4x4, 3x3) (wino4.hip)
-                t4 = ops._time_call(lambda: ops.conv2d_raw(x, wp, co, (kk, kk), 1, kk // 2, False, (hw, hw), bias=b, flags=3, algo=wid + 2), reps=3)
+                t4 = tune.time_call(lambda: ops.conv2d_raw(x, wp, co, (kk, kk), 1, kk // 2, False, (hw, hw), bias=b, flags=3, algo=wid + 2), reps=3)
             except L.CrdrHipError:
                 pass
         f4 = f"   F(4x4) {t4 * 1e3:8.1f} us ({fl / t4 / 1e9:6.1f} TF-eq) x{best[0] / t4:.2f}" if t4 else ""

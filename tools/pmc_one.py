@@ -5,7 +5,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from crdr_amd.hip import ops, lib as L  # noqa: E402
+from crdr_amd.hip import ops, tune, lib as L  # noqa: E402
 import ctypes as C  # noqa: E402
 
 ci, h, co, k, s, tr = [int(v) for v in sys.argv[1:7]]
@@ -24,11 +24,11 @@ y = ops.conv2d_raw(x, wf, co, (k, k), s, p, bool(tr), (oh, oh))
 if algo < 0:   # autotune this shape first (trial launches come before the measured ones)
     ops.AUTOTUNE = True
 elif algo:
-    ops._algo_cache.clear()
+    tune.algo_cache.clear()
     ops.AUTOTUNE = True
     key_hook = {}
-    orig = ops._autotune
-    ops._autotune = lambda key, *a, **k: (ops._algo_cache.__setitem__(key, algo) or algo)
+    orig = tune.autotune
+    tune.autotune = lambda key, *a, **k: (tune.algo_cache.__setitem__(key, algo) or algo)
 for _ in range(10):
     ops.conv2d_raw(x, wf, co, (k, k), s, p, bool(tr), (oh, oh), out=y)
 torch.cuda.synchronize()

@@ -1,6 +1,6 @@
 #!/bin/bash
 # The perf-database entries of `precision: bf16x6` (run from the repo root on the GPU box): the stage-3 and stage-1 steps in that mode with the
-# tuner live (cold caches, best of 2; every candidate must agree with the mode's built-in plan, ops._autotune), on top of the shipped database
+# tuner live (cold caches, best of 2; every candidate must agree with the mode's built-in plan, tune.autotune), on top of the shipped database
 # -- whose exact-fp32 entries are keyed differently (the mode travels in the conv keys' flags and in a suffix of the weight-gradient keys) and are
 # not touched.  The saved database = the shipped entries + the new ones: review, then copy it to crdr_amd/hip/tune_gfx950.json.
 set -x

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Rebuild the shipped perf database on the GPU box (run from the repo root): the 3x3 / 5x5 launches are timed again (cold caches,
-# best of 3) on top of the shipped entries -- every candidate also has to agree with the built-in plan's result (ops._autotune) --
+# best of 3) on top of the shipped entries -- every candidate also has to agree with the built-in plan's result (tune.autotune) --
 # then one confirmation run and the acceptance run: the full-size oracle steps and the plan replay on the candidate database.
 # Since round 6 the acceptance run is DETERMINISTIC: the full-size steps hand the product's ReLU masks to the oracle
 # (tests/test_gpu_step.py, UPSTREAM_IMPOSED_TOL), so the upstream gradients no longer depend on which masks a plan set happens to flip --
