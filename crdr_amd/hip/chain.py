@@ -16,7 +16,7 @@ The forward issues exactly the launches the per-layer path issued (same kernels,
 from __future__ import annotations
 
 import itertools
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Sequence
 
 import torch
 
@@ -64,6 +64,10 @@ class ChainSpec:
     def unit(self, g, u) -> Unit:
         return self.groups[g][u]
 
+    def layers(self, u, li) -> List[Layer]:
+        """layer li of unit u in each of the G chains"""
+        return [grp[u].layers[li] for grp in self.groups]
+
     def parameters(self):
         out = []
         for grp in self.groups:
@@ -86,38 +90,41 @@ class ChainSpec:
         return self._dv
 
 
-def _geom(conv, h, w):
-    s = conv.spec
-    oh, ow = s.out_hw(h, w)
-    return oh, ow
-
-
 def _flags(act):
     return L.EPI_RELU if act == "relu" else L.EPI_LRELU if act == "lrelu" else 0
 
 
-def _bufs(m, c, g, device):
-    """g dense [M][c'] buffers (c' = c rounded up to 4, padding lanes zeroed): one per parallel chain, same pixel stride"""
-    cp = (c + 3) // 4 * 4
-    mk = torch.zeros if cp != c else torch.empty
-    return [mk((m, cp), dtype=torch.float32, device=device) for _ in range(g)], cp
+class Acts:
+    """One tensor of each of the G parallel chains -- a layer's outputs, or their gradients -- in fresh dense [M][c'] buffers of one pixel
+    stride (c' = c rounded up to 4, padding lanes zeroed)."""
+    __slots__ = ("bufs", "cp", "c", "n", "h", "w")
 
+    def __init__(self, g, n, h, w, c, device):
+        self.cp, self.c, self.n, self.h, self.w = (c + 3) // 4 * 4, c, n, h, w
+        mk = torch.zeros if self.cp != c else torch.empty
+        self.bufs = [mk((n * h * w, self.cp), dtype=torch.float32, device=device) for _ in range(g)]
 
-def _nchw(buf, n, h, w, c):
-    return buf.view(n, h, w, buf.shape[1]).permute(0, 3, 1, 2)[:, :c]
+    def vs(self) -> List[V]:
+        return [V(b.data_ptr(), self.cp, self.c) for b in self.bufs]
+
+    def nchw(self) -> List[torch.Tensor]:
+        return [b.view(self.n, self.h, self.w, self.cp).permute(0, 3, 1, 2)[:, :self.c] for b in self.bufs]
 
 
 # A forward pass kept for a SECOND backward (round 6).  The stage-3 step evaluates the discriminator on the reconstruction twice with unchanged
 # weights: in the generator phase (D frozen, the adversarial term's gradient flows to the image) and in the discriminator phase (image detached,
 # the gradient flows to D's weights) -- the reference even does it three times (multirate_hr_rgan_beta_cond_rate_distortion_trainer.py:52, 92,
 # 98).  Same input, same weights, same launches: the activations of the first pass ARE those of the second.  With KEEP_HANDLES a list, every
-# chain forward appends a handle (spec, saved activations, geometry, input, outputs); run_chain_reuse(handle) is then an autograd node whose
+# chain forward appends a handle (spec, saved activations, geometry, input); run_chain_reuse(handle) is then an autograd node whose
 # forward launches nothing and whose backward is _ChainFn.backward on the kept activations.
 KEEP_HANDLES = None
 
 
 class ChainHandle:
-    __slots__ = ("spec", "saved", "geom", "x", "oc")
+    __slots__ = ("spec", "saved", "geom", "x")
+
+    def __init__(self, spec, saved, geom, x):
+        self.spec, self.saved, self.geom, self.x = spec, saved, geom, x
 
 
 class _KeptCtx:
@@ -127,6 +134,57 @@ class _KeptCtx:
 
     def __init__(self, ctx):
         self.spec, self.saved_acts, self.geom, self.nrest, self.saved_tensors = ctx.spec, ctx.saved_acts, ctx.geom, ctx.nrest, ctx.saved_tensors
+
+
+def _bias_slot(cv):
+    return HF.grad_slot(cv.bias) if (cv.bias is not None and cv.bias.requires_grad) else None
+
+
+def _colsum_targets(layers: Sequence[Layer], dvs):
+    """Where the column sums of the gradient of `layers`' outputs go, per chain: (address for the pre-mask sum = the beta vector added
+    after the activation, address for the post-mask sum = the bias)"""
+    slots = [_bias_slot(b.conv) for b in layers]
+    return [(None if b.vec_index is None else dvs[b.vec_index].data_ptr(), None if s is None else s.data_ptr()) for b, s in zip(layers, slots)]
+
+
+def _layer_input(saved, xin, u, li):
+    """What layer li of unit u read, as (Vs, (h, w), channels): the layer below it, the previous unit's output, or the chain input `xin`"""
+    if u == 0 and li == 0:
+        return xin
+    a = saved[u][li - 1] if li else saved[u - 1][-1]
+    return a.vs(), (a.h, a.w), a.c
+
+
+def _output_grad(spec: ChainSpec, out: Acts, douts, scale, shift, dvs, device):
+    """The gradient at the chain output(s) -> (Vs, tensors, d scale, d shift), with the bias / beta-vector gradients of the last layers taken.
+    An affine epilogue on the last conv (InterpChAtt) is undone by the fused elementwise pass, which also yields d scale / d shift and the
+    column sums of the pre-affine gradient."""
+    last = spec.layers(spec.U - 1, -1)
+    if spec.affine:
+        lay = last[0]
+        _, gres, _, cs = ops.epilogue_bwd(douts[0], out.nchw()[0], L.EPI_AFFINE | L.EPI_RES, scale=scale, shift=shift, need_dz=False,
+                                         dbias_accum=_bias_slot(lay.conv))
+        gres, ldg = ops.nhwc(gres)
+        if lay.vec_index is not None:
+            dvs[lay.vec_index].add_(cs[0])
+        return [V(gres.data_ptr(), ldg, out.c)], [gres], cs[2], cs[3]
+    ts = [d if d is not None else torch.zeros_like(o) for d, o in zip(douts, out.nchw())]
+    pairs = [ops.nhwc(t) for t in ts]
+    if len({ld for _, ld in pairs}) > 1:   # a grouped launch needs one pixel stride: repack densely
+        dense = Acts(spec.G, out.n, out.h, out.w, out.c, device)
+        dz_v, dz_t = dense.vs(), dense.nchw()
+        for d, t in zip(dz_t, ts):
+            d.copy_(t)
+    else:
+        dz_t = [t for t, _ in pairs]
+        dz_v = [V(t.data_ptr(), ld, out.c) for t, ld in pairs]
+    for lay, t in zip(last, dz_t):   # bias / beta-vector gradient of the chain's last layer: a plain column sum
+        tgt = _bias_slot(lay.conv)
+        if tgt is not None:
+            ops.colsum(t, tgt, accumulate=True)
+        if lay.vec_index is not None:
+            ops.colsum(t, dvs[lay.vec_index], accumulate=True)
+    return dz_v, dz_t, None, None
 
 
 class _ChainFn(torch.autograd.Function):
@@ -142,24 +200,22 @@ class _ChainFn(torch.autograd.Function):
         n, c, h, w = x.shape
         dev = x.device
         G = spec.G
-        xin = [V(x.data_ptr(), ldx, c)] * G
-        saved = []   # per unit: list over layers of (buffer tensor, width, (n, h, w) of the OUTPUT)
-        cur, cur_hw = xin, (h, w)
-        unit_inputs = []
+        cur, cur_hw = [V(x.data_ptr(), ldx, c)] * G, (h, w)
+        saved = []   # per unit: the Acts of every layer's output
         for u in range(spec.U):
-            unit_inputs.append((cur, cur_hw))
+            unit_in = cur
             acts = []
             nl = len(spec.unit(0, u).layers)
             for li in range(nl):
                 lay0 = spec.unit(0, u).layers[li]
-                convs = [spec.unit(g, u).layers[li].conv for g in range(G)]
+                convs = [lay.conv for lay in spec.layers(u, li)]
                 sp = convs[0].spec
                 ih, iw = cur_hw
                 oh, ow = sp.out_hw(ih, iw)
-                bufs, cp = _bufs(n * oh * ow, sp.out_ch, G, dev)
-                ys = [V(b.data_ptr(), cp, sp.out_ch) for b in bufs]
+                out = Acts(G, n, oh, ow, sp.out_ch, dev)
+                ys = out.vs()
                 last = li == nl - 1
-                ress = unit_inputs[u][0] if (last and spec.unit(0, u).residual) else None
+                ress = unit_in if (last and spec.unit(0, u).residual) else None
                 aff = spec.affine and last and u == spec.U - 1
                 packs = [cv.spec.pack(cv.weight, False) for cv in convs]
                 ops.conv_multi(n, ih, iw, oh, ow, cur, [pk.data_ptr() for pk in packs], ys, sp.out_ch, sp.k, sp.stride, sp.pad,
@@ -169,21 +225,17 @@ class _ChainFn(torch.autograd.Function):
                                scale=scale.data_ptr() if aff else None, shift=shift.data_ptr() if aff else None,
                                flags=_flags(lay0.act) | (L.EPI_VEC2 if lay0.vec_index is not None else 0),
                                wlayout=1 if sp.smallc else 0, device=dev, label=spec.name)
-                acts.append((bufs, cp, (n, oh, ow)))
+                acts.append(out)
                 if ops.RELU_MASK_SINK is not None and lay0.act == "relu" and any(ctx.needs_input_grad):   # (a no-grad pass -- the high-rate reconstruction -- has no backward to take masks for)
-                    for g in range(G):   # (test hook: the activations this node's backward takes its ReLU masks from)
-                        ops.RELU_MASK_SINK(convs[g].weight, _nchw(bufs[g], n, oh, ow, sp.out_ch), None if lay0.vec_index is None else vecs[lay0.vec_index])
+                    for cv, t in zip(convs, out.nchw()):   # (test hook: the activations this node's backward takes its ReLU masks from)
+                        ops.RELU_MASK_SINK(cv.weight, t, None if lay0.vec_index is None else vecs[lay0.vec_index])
                 cur, cur_hw = ys, (oh, ow)
             saved.append(acts)
         ctx.spec, ctx.saved_acts, ctx.geom = spec, saved, (n, c, h, w, ldx)
         ctx.save_for_backward(x, scale, shift, *vecs)
-        bufs, cp, (n_, oh, ow) = saved[-1][-1]
-        oc = spec.unit(0, spec.U - 1).layers[-1].conv.spec.out_ch
         if KEEP_HANDLES is not None and not vecs and scale is None:
-            hd = ChainHandle()
-            hd.spec, hd.saved, hd.geom, hd.x, hd.oc = spec, saved, (n, c, h, w, ldx), x, oc
-            KEEP_HANDLES.append(hd)
-        return tuple(_nchw(b, n_, oh, ow, oc) for b in bufs)
+            KEEP_HANDLES.append(ChainHandle(spec, saved, ctx.geom, x))
+        return tuple(saved[-1][-1].nchw())
 
     @staticmethod
     def backward(ctx, *douts):
@@ -193,140 +245,77 @@ class _ChainFn(torch.autograd.Function):
         dev = x.device
         G = spec.G
         saved = ctx.saved_acts
+        xin = ([V(x.data_ptr(), ldx, c)] * G, (h, w), c)
         q = ops.colsum_queue(dev)
         dvs = []
         if vecs:
             flat, dvs = spec.dv_buffers([v.numel() for v in vecs], dev)
             flat.zero_()
-        prev_defer = ops.WGRAD_DEFER
-        local = prev_defer is None or prev_defer.device != dev
-        if local:
-            from .charm import _local_defer
-            d = _local_defer.get(dev)
-            if d is None:
-                d = _local_defer[dev] = ops.DeferredWgrad(dev, arena_bytes=256 << 20)
-            ops.WGRAD_DEFER = d
-
-        def views(bufs, cp, cc, nn, hh, ww):
-            """per-problem (V, NCHW tensor view) of the G dense buffers"""
-            return [V(b.data_ptr(), cp, cc) for b in bufs], [_nchw(b, nn, hh, ww, cc) for b in bufs]
-
-        def bias_slot(cv):
-            return HF.grad_slot(cv.bias) if (cv.bias is not None and cv.bias.requires_grad) else None
         try:
-            # ---- gradient at the chain output(s).  An affine epilogue on the last conv (InterpChAtt) is undone by the
-            # fused elementwise pass, which also yields d scale / d shift and the column sums of the pre-affine gradient.
-            obufs, cp, (n_, oh, ow) = saved[-1][-1]
-            last_layers = [spec.unit(g, spec.U - 1).layers[-1] for g in range(G)]
-            oc = last_layers[0].conv.spec.out_ch
-            dscale = dshift = None
-            if spec.affine:
-                out = _nchw(obufs[0], n_, oh, ow, oc)
-                lay = last_layers[0]
-                _, gres, _, cs = ops.epilogue_bwd(douts[0], out, L.EPI_AFFINE | L.EPI_RES, scale=scale, shift=shift, need_dz=False,
-                                                 dbias_accum=bias_slot(lay.conv))
-                gres, ldg = ops.nhwc(gres)
-                dz_v, dz_t = [V(gres.data_ptr(), ldg, oc)], [gres]
-                dscale, dshift = cs[2], cs[3]
-                if lay.vec_index is not None:
-                    dvs[lay.vec_index].add_(cs[0])
-            else:
-                ts = [douts[g] if douts[g] is not None else torch.zeros_like(_nchw(obufs[g], n_, oh, ow, oc)) for g in range(G)]
-                pairs = [ops.nhwc(t) for t in ts]
-                if len({ld for _, ld in pairs}) > 1:   # a grouped launch needs one pixel stride: repack densely
-                    wbs, cpp = _bufs(n_ * oh * ow, oc, G, dev)
-                    for g in range(G):
-                        _nchw(wbs[g], n_, oh, ow, oc).copy_(ts[g])
-                    dz_v, dz_t = views(wbs, cpp, oc, n_, oh, ow)
-                else:
-                    dz_t = [t for t, _ in pairs]
-                    dz_v = [V(t.data_ptr(), ld, oc) for t, ld in pairs]
-                for g in range(G):  # bias / beta-vector gradient of the chain's last layer: a plain column sum
-                    tgt = bias_slot(last_layers[g].conv)
-                    if tgt is not None:
-                        ops.colsum(dz_t[g], tgt, accumulate=True)
-                    if last_layers[g].vec_index is not None:
-                        ops.colsum(dz_t[g], dvs[last_layers[g].vec_index], accumulate=True)
-            dz_hw = (oh, ow)
-            dx_out = None
-            # ---- units in reverse
-            for u in reversed(range(spec.U)):
-                layers0 = spec.unit(0, u).layers
-                nl = len(layers0)
-                if u == 0:
-                    uin, (uh, uw), uin_c = [V(x.data_ptr(), ldx, c)] * G, (h, w), c
-                else:
-                    pbs, pcp, (_, ph_, pw_) = saved[u - 1][-1]
-                    uin_c = spec.unit(0, u - 1).layers[-1].conv.spec.out_ch
-                    uin, (uh, uw) = [V(b.data_ptr(), pcp, uin_c) for b in pbs], (ph_, pw_)
-                g_unit, g_unit_keep = dz_v, dz_t   # gradient wrt the unit output (kept alive: the residual operand of the
-                # unit's first input-gradient conv reads it after the per-layer gradients have been replaced)
-                assert layers0[-1].act is None, "the last layer of a unit carries no activation"
-                for li in reversed(range(nl)):
-                    convs = [spec.unit(g, u).layers[li].conv for g in range(G)]
-                    sp = convs[0].spec
-                    if li == 0:
-                        lin, (ih, iw), lin_c = uin, (uh, uw), uin_c
-                    else:
-                        abs_, acp, (_, ah, aw) = saved[u][li - 1]
-                        lin_c = layers0[li - 1].conv.spec.out_ch
-                        lin, (ih, iw) = [V(b.data_ptr(), acp, lin_c) for b in abs_], (ah, aw)
-                    oh_, ow_ = dz_hw
-                    wts = [cv.weight for cv in convs]
-                    if wts[0].requires_grad:   # weight gradient: (dz, layer input)
-                        gp = [HF.grad_slot(wt).data_ptr() for wt in wts]
-                        if sp.transposed:
-                            ops.wgrad_multi(n, ih, iw, oh_, ow_, lin, dz_v, gp, wts[0].shape[0], wts[0].shape[1], sp.k, sp.stride, sp.pad,
-                                            device=dev, label=spec.name)
-                        else:
-                            ops.wgrad_multi(n, oh_, ow_, ih, iw, dz_v, lin, gp, wts[0].shape[0], wts[0].shape[1], sp.k, sp.stride, sp.pad,
-                                            device=dev, label=spec.name)
-                    first = li == 0
-                    if first and u == 0 and not ctx.needs_input_grad[0]:
-                        break
-                    if first and u == 0 and (not sp.transposed) and sp.in_ch <= 4 and sp.k[0] * sp.k[1] > 1:
-                        assert G == 1   # RGB image gradient: GEMM + gather path (nothing to fuse at the chain input)
-                        dx_out = [HF.scatter_conv(dz_t[0], convs[0].weight, None, sp, (ih, iw))]
-                        break
-                    # input gradient, with the backward of the layer below (and of the residual) fused in
-                    below = [spec.unit(g, u).layers[li - 1] for g in range(G)] if not first else None
-                    gbufs, ocp = _bufs(n * ih * iw, lin_c, G, dev)
-                    ys, yts = views(gbufs, ocp, lin_c, n, ih, iw)
-                    flags, masks, vec2 = 0, None, None
-                    targets = [(None, None)] * G    # (address for the pre-mask sum, address for the post-mask sum)
-                    if below is not None:
-                        b0 = below[0]
-                        if b0.act is not None:
-                            flags |= L.EPI_RELUMASK if b0.act == "relu" else L.EPI_LRELUMASK
-                            masks = lin
-                            if b0.vec_index is not None:
-                                flags |= L.EPI_MASKOFF
-                                vec2 = vecs[b0.vec_index].data_ptr()
-                        targets = [(dvs[b.vec_index].data_ptr() if b.vec_index is not None else None,
-                                    None if bias_slot(b.conv) is None else bias_slot(b.conv).data_ptr()) for b in below]
-                    elif u > 0:   # this launch produces the gradient of unit u-1's output = of its last layer
-                        prev = [spec.unit(g, u - 1).layers[-1] for g in range(G)]
-                        targets = [(dvs[b.vec_index].data_ptr() if b.vec_index is not None else None,
-                                    None if bias_slot(b.conv) is None else bias_slot(b.conv).data_ptr()) for b in prev]
-                    ress = g_unit if (first and spec.unit(0, u).residual) else None
-                    want_cs = any(a is not None or b is not None for a, b in targets)
-                    packs = [cv.spec.pack(cv.weight, True) for cv in convs]
-                    cs = ops.conv_multi(n, oh_, ow_, ih, iw, dz_v, [pk.data_ptr() for pk in packs], ys, lin_c, sp.k, sp.stride, sp.pad,
-                                        not sp.transposed, wrows=packs[0].shape[1], wcols=packs[0].shape[2], masks=masks, ress=ress,
-                                        vec2=vec2, flags=flags, colsum=want_cs, wlayout=1 if sp.smallc_dgrad else 0, device=dev,
-                                        label=spec.name + ".bwd")
-                    if want_cs:
-                        for g in range(G):
-                            ptr, rows, ld = cs[g]
-                            q.add(ptr, rows, ld, lin_c, targets[g][0], targets[g][1], True)
-                    dz_v, dz_t, dz_hw = ys, yts, (ih, iw)
-                if u == 0 and dx_out is None and ctx.needs_input_grad[0]:
-                    dx_out = dz_t
-            q.flush(spec.site)
-            if local:
-                ops.WGRAD_DEFER.flush(("chain-local", dev.index))
-        finally:
-            ops.WGRAD_DEFER = prev_defer
+            with ops.local_wgrad_defer(dev, ("chain-local", dev.index)):
+                dz_v, dz_t, dscale, dshift = _output_grad(spec, saved[-1][-1], douts, scale, shift, dvs, dev)
+                dz_hw = (saved[-1][-1].h, saved[-1][-1].w)
+                dx_out = None
+                # ---- units in reverse
+                for u in reversed(range(spec.U)):
+                    layers0 = spec.unit(0, u).layers
+                    g_unit, g_unit_keep = dz_v, dz_t   # gradient wrt the unit output (kept alive: the residual operand of the
+                    # unit's first input-gradient conv reads it after the per-layer gradients have been replaced)
+                    assert layers0[-1].act is None, "the last layer of a unit carries no activation"
+                    for li in reversed(range(len(layers0))):
+                        convs = [lay.conv for lay in spec.layers(u, li)]
+                        sp = convs[0].spec
+                        lin, (ih, iw), lin_c = _layer_input(saved, xin, u, li)
+                        oh_, ow_ = dz_hw
+                        wts = [cv.weight for cv in convs]
+                        if wts[0].requires_grad:   # weight gradient: (dz, layer input)
+                            gp = [HF.grad_slot(wt).data_ptr() for wt in wts]
+                            if sp.transposed:
+                                ops.wgrad_multi(n, ih, iw, oh_, ow_, lin, dz_v, gp, wts[0].shape[0], wts[0].shape[1], sp.k, sp.stride, sp.pad,
+                                                device=dev, label=spec.name)
+                            else:
+                                ops.wgrad_multi(n, oh_, ow_, ih, iw, dz_v, lin, gp, wts[0].shape[0], wts[0].shape[1], sp.k, sp.stride, sp.pad,
+                                                device=dev, label=spec.name)
+                        first = li == 0
+                        if first and u == 0 and not ctx.needs_input_grad[0]:
+                            break
+                        if first and u == 0 and (not sp.transposed) and sp.in_ch <= 4 and sp.k[0] * sp.k[1] > 1:
+                            assert G == 1   # RGB image gradient: GEMM + gather path (nothing to fuse at the chain input)
+                            dx_out = [HF.scatter_conv(dz_t[0], convs[0].weight, None, sp, (ih, iw))]
+                            break
+                        # input gradient, with the backward of the layers that produced this input fused in: the layer below, or (first
+                        # layer of a unit) the last layer of the unit before, which carries no activation -- and the residual's
+                        dgrad = Acts(G, n, ih, iw, lin_c, dev)
+                        ys, yts = dgrad.vs(), dgrad.nchw()
+                        flags, masks, vec2 = 0, None, None
+                        targets = [(None, None)] * G
+                        if not (first and u == 0):
+                            below = spec.layers(u, li - 1) if not first else spec.layers(u - 1, -1)
+                            targets = _colsum_targets(below, dvs)
+                            b0 = below[0]
+                            if b0.act is not None:
+                                flags |= L.EPI_RELUMASK if b0.act == "relu" else L.EPI_LRELUMASK
+                                masks = lin
+                                if b0.vec_index is not None:
+                                    flags |= L.EPI_MASKOFF
+                                    vec2 = vecs[b0.vec_index].data_ptr()
+                        ress = g_unit if (first and spec.unit(0, u).residual) else None
+                        want_cs = any(a is not None or b is not None for a, b in targets)
+                        packs = [cv.spec.pack(cv.weight, True) for cv in convs]
+                        cs = ops.conv_multi(n, oh_, ow_, ih, iw, dz_v, [pk.data_ptr() for pk in packs], ys, lin_c, sp.k, sp.stride, sp.pad,
+                                            not sp.transposed, wrows=packs[0].shape[1], wcols=packs[0].shape[2], masks=masks, ress=ress,
+                                            vec2=vec2, flags=flags, colsum=want_cs, wlayout=1 if sp.smallc_dgrad else 0, device=dev,
+                                            label=spec.name + ".bwd")
+                        if want_cs:
+                            for (ptr, rows, ld), (pre, post) in zip(cs, targets):
+                                q.add(ptr, rows, ld, lin_c, pre, post, True)
+                        dz_v, dz_t, dz_hw = ys, yts, (ih, iw)
+                    if u == 0 and dx_out is None and ctx.needs_input_grad[0]:
+                        dx_out = dz_t
+                q.flush(spec.site)
+        except BaseException:
+            q.drop()   # (like the scope's weight-gradient jobs: the next backward on this device must not finish stale column sums)
+            raise
         dx = None
         if dx_out is not None:
             dx = dx_out[0]
@@ -355,8 +344,7 @@ class _ChainReuseFn(torch.autograd.Function):
         ctx.spec, ctx.saved_acts, ctx.geom = handle.spec, handle.saved, handle.geom
         ctx.nrest = len(params)
         ctx.save_for_backward(handle.x, None, None)
-        bufs, cp, (n_, oh, ow) = handle.saved[-1][-1]
-        return tuple(_nchw(b, n_, oh, ow, handle.oc) for b in bufs)
+        return tuple(handle.saved[-1][-1].nchw())
 
     @staticmethod
     def backward(ctx, *douts):

@@ -36,7 +36,7 @@ slice k -- every transform of a later slice -- are a PREFIX of each half.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -85,8 +85,7 @@ class CharmPlan:
         self.slot = {t: k for k, t in enumerate(order)}
         self.NT = len(order)
         self.signature = self._signature()
-        self._fwd = None
-        self._bwd = None
+        self._packs = {}
         self._tables = None
 
     # ---- parameters
@@ -118,110 +117,61 @@ class CharmPlan:
         lo, cnt = (0, 2 * nc) if half == "mu" else (self.n_mu, nc)
         return lo, self.order[lo:lo + cnt]
 
+    def halves(self):
+        """(pack key, first slot, slot count) of the two hoisted hyper-prior convs"""
+        return ("hyp_mu", 0, self.n_mu), ("hyp_sc", self.n_mu, self.n_sc)
+
     # ---- packs
-    def _alloc(self, *shape):
-        return torch.empty(shape, dtype=torch.float32, device=self.device)
+    def pack_layout(self):
+        """Every weight pack of the engine, once and in table order: (key, taps, blocks).  A block is (conv weight [I][J'][kh][kw], j0, j1):
+        input channels [j0, j1) of that conv; the blocks of a pack are N-concatenated in list order, so in forward orientation the pack
+        is [taps][len(blocks) * I][J = j1 - j0]."""
+        hm, sc = self.hm, self.sc
+        w = lambda kind, i, layer: self.conv(kind, i, layer).weight
+        t1, t2, t3 = (k[0] * k[1] for k in (self.k1, self.k2, self.k3))
+        for name, lo, n in self.halves():   # the hoisted hyper-prior parts, in slot order
+            yield name, t1, [(w(kind, i, 0), 0, hm) for kind, i in self.order[lo:lo + n]]
+        for k in range(self.ms):            # the support parts: decoded slice k -> every later transform, in slot order
+            for half in ("mu", "sc"):
+                _, cons = self.consumers(k, half)
+                if cons:
+                    yield ("sup_" + half, k), t1, [(w(kind, j, 0), hm + k * sc, hm + (k + 1) * sc) for kind, j in cons]
+        for kind in ("mean", "scale", "lrp"):
+            for i in range(self.S):
+                if i == 0 and kind != "lrp":      # slice 0: the whole first conv directly
+                    yield (kind, 0, "l1"), t1, [(w(kind, 0, 0), 0, hm)]
+                if kind == "lrp":                 # the slice's own pre-correction latent: the last part of its first conv
+                    j0 = hm + self.sup(i)
+                    yield (kind, i, "own"), t1, [(w(kind, i, 0), j0, j0 + sc)]
+                yield (kind, i, "l2"), t2, [(w(kind, i, 1), 0, self.C1)]
+                yield (kind, i, "l3"), t3, [(w(kind, i, 2), 0, self.C2)]
+
+    def _build_packs(self, transposed: bool):
+        """-> ({key: address}, entries to keep fresh, buffers).  transposed False: the forward operands [t][n * I][J]; True: the
+        input-gradient operands [t][J][n * I] (the blocks K-concatenated)."""
+        addr, ents, keep = {}, [], []
+        for key, taps, blocks in self.pack_layout():
+            n, I, J = len(blocks), blocks[0][0].shape[0], blocks[0][2] - blocks[0][1]
+            buf = torch.empty((taps, J, n * I) if transposed else (taps, n * I, J), dtype=torch.float32, device=self.device)
+            addr[key] = buf.data_ptr()
+            keep.append(buf)
+            for blk, (w, j0, j1) in enumerate(blocks):
+                ents.append(packs.sub_pack(w, j0, j1, buf, blk * I * (1 if transposed else J), J if transposed else I, I if transposed else J,
+                                           transposed, dld=buf.shape[2], tstride=buf.shape[1] * buf.shape[2]))
+        return addr, ents, keep
+
+    def _cached_packs(self, transposed: bool):
+        if transposed not in self._packs:     # lazy per direction: an inference process never builds the input-gradient packs
+            self._packs[transposed] = self._build_packs(transposed)
+        return self._packs[transposed]
 
     def fwd_packs(self):
-        """Forward operands: packs[(kind, i, what)] = address; entries to keep fresh."""
-        if self._fwd is not None:
-            return self._fwd
-        S, ms, C1, C2, hm, sc = self.S, self.ms, self.C1, self.C2, self.hm, self.sc
-        t1, t2, t3 = self.k1[0] * self.k1[1], self.k2[0] * self.k2[1], self.k3[0] * self.k3[1]
-        ents, addr, keep = [], {}, []
-        # hoisted hyper parts: [t1][n * C1][hm]
-        for name, lo, n in (("hyp_mu", 0, self.n_mu), ("hyp_sc", self.n_mu, self.n_sc)):
-            buf = self._alloc(t1, n * C1, hm)
-            keep.append(buf)
-            addr[name] = buf.data_ptr()
-            for k in range(n):
-                kind, i = self.order[lo + k]
-                ents.append(packs.sub_pack(self.conv(kind, i, 0).weight, 0, hm, buf, k * C1 * hm, C1, hm, False, dld=hm, tstride=n * C1 * hm))
-        # support parts: decoded slice k -> every later transform, N-concatenated in slot order: [t1][n * C1][sc]
-        for k in range(ms):
-            for half in ("mu", "sc"):
-                lo, cons = self.consumers(k, half)
-                if not cons:
-                    continue
-                n = len(cons)
-                buf = self._alloc(t1, n * C1, sc)
-                keep.append(buf)
-                addr[("sup_" + half, k)] = buf.data_ptr()
-                for idx, (kind, j) in enumerate(cons):
-                    ents.append(packs.sub_pack(self.conv(kind, j, 0).weight, hm + k * sc, hm + (k + 1) * sc, buf, idx * C1 * sc, C1, sc, False,
-                                            dld=sc, tstride=n * C1 * sc))
-        for kind in ("mean", "scale", "lrp"):
-            for i in range(S):
-                w = self.conv(kind, i, 0).weight
-                if i == 0 and kind != "lrp":      # slice 0: the whole first conv directly
-                    b = self._alloc(t1, C1, hm)
-                    ents.append(packs.sub_pack(w, 0, hm, b, 0, C1, hm, False))
-                    addr[(kind, 0, "l1")] = b.data_ptr()
-                    keep.append(b)
-                if kind == "lrp":                 # the slice's own pre-correction latent: the last part of its first conv
-                    s = self.sup(i)
-                    b = self._alloc(t1, C1, sc)
-                    ents.append(packs.sub_pack(w, hm + s, hm + s + sc, b, 0, C1, sc, False))
-                    addr[(kind, i, "own")] = b.data_ptr()
-                    keep.append(b)
-                w2, w3 = self.conv(kind, i, 1).weight, self.conv(kind, i, 2).weight
-                b2, b3 = self._alloc(t2, C2, C1), self._alloc(t3, sc, C2)
-                ents.append(packs.sub_pack(w2, 0, C1, b2, 0, C2, C1, False))
-                ents.append(packs.sub_pack(w3, 0, C2, b3, 0, sc, C2, False))
-                addr[(kind, i, "l2")], addr[(kind, i, "l3")] = b2.data_ptr(), b3.data_ptr()
-                keep += [b2, b3]
-        self._fwd = (addr, ents, keep)
-        return self._fwd
+        """Forward operands: (packs[key] = address, entries to keep fresh, buffers)."""
+        return self._cached_packs(False)
 
     def bwd_packs(self):
-        """Input-gradient operands ([tap][in][out])."""
-        if self._bwd is not None:
-            return self._bwd
-        S, ms, C1, C2, hm, sc, T = self.S, self.ms, self.C1, self.C2, self.hm, self.sc, self.T
-        t1, t2, t3 = self.k1[0] * self.k1[1], self.k2[0] * self.k2[1], self.k3[0] * self.k3[1]
-        ents, addr, keep = [], {}, []
-        for name, lo, n in (("hyp_mu", 0, self.n_mu), ("hyp_sc", self.n_mu, self.n_sc)):
-            buf = self._alloc(t1, hm, n * C1)
-            keep.append(buf)
-            addr[name] = buf.data_ptr()
-            for k in range(n):
-                kind, i = self.order[lo + k]
-                ents.append(packs.sub_pack(self.conv(kind, i, 0).weight, 0, hm, buf, k * C1, hm, C1, True, dld=n * C1, tstride=hm * n * C1))
-        # support parts, K-concatenated over the consumers of slice k: [t1][sc][n * C1]
-        for k in range(ms):
-            for half in ("mu", "sc"):
-                lo, cons = self.consumers(k, half)
-                if not cons:
-                    continue
-                n = len(cons)
-                buf = self._alloc(t1, sc, n * C1)
-                keep.append(buf)
-                addr[("sup_" + half, k)] = buf.data_ptr()
-                for idx, (kind, j) in enumerate(cons):
-                    ents.append(packs.sub_pack(self.conv(kind, j, 0).weight, hm + k * sc, hm + (k + 1) * sc, buf, idx * C1, sc, C1, True,
-                                            dld=n * C1, tstride=sc * n * C1))
-        for kind in ("mean", "scale", "lrp"):
-            for i in range(S):
-                w = self.conv(kind, i, 0).weight
-                if i == 0 and kind != "lrp":
-                    b = self._alloc(t1, hm, C1)
-                    ents.append(packs.sub_pack(w, 0, hm, b, 0, hm, C1, True))
-                    addr[(kind, 0, "l1")] = b.data_ptr()
-                    keep.append(b)
-                if kind == "lrp":
-                    s = self.sup(i)
-                    b = self._alloc(t1, sc, C1)
-                    ents.append(packs.sub_pack(w, hm + s, hm + s + sc, b, 0, sc, C1, True))
-                    addr[(kind, i, "own")] = b.data_ptr()
-                    keep.append(b)
-                w2, w3 = self.conv(kind, i, 1).weight, self.conv(kind, i, 2).weight
-                b2, b3 = self._alloc(t2, C1, C2), self._alloc(t3, C2, sc)
-                ents.append(packs.sub_pack(w2, 0, C1, b2, 0, C1, C2, True))
-                ents.append(packs.sub_pack(w3, 0, C2, b3, 0, C2, sc, True))
-                addr[(kind, i, "l2")], addr[(kind, i, "l3")] = b2.data_ptr(), b3.data_ptr()
-                keep += [b2, b3]
-        self._bwd = (addr, ents, keep)
-        return self._bwd
+        """Input-gradient operands ([tap][in][out]), same keys."""
+        return self._cached_packs(True)
 
     def bias_tables(self):
         """Device pointer tables for crdr_colsum_scatter: L1 / L2 biases in slot order, L3 biases in MSL order."""
@@ -251,10 +201,11 @@ class CharmRun:
     """One pass over a batch: owns the wide buffers; `forward()` runs the whole schedule, the stage methods let the
     decoder interleave the host entropy coder."""
 
-    def __init__(self, plan: CharmPlan, hyper_mu: torch.Tensor, hyper_sc: Optional[torch.Tensor]):
+    def __init__(self, plan: CharmPlan, hyper_mu: torch.Tensor, hyper_sc: Optional[torch.Tensor], scale_bound: float, lik_bound: float):
         """hyper_mu / hyper_sc: the two halves of the hyper-decoder output (channel slices of one tensor are fine);
-        hyper_sc = None: reconstruction only (no scale transforms, no likelihoods)."""
+        hyper_sc = None: reconstruction only (no scale transforms, no likelihoods).  The two bounds are the Gaussian conditional's."""
         self.p = plan
+        self.scale_bound, self.lik_bound = float(scale_bound), float(lik_bound)
         hyper_mu, ldm = ops.nhwc(hyper_mu)
         n, c, h, w = hyper_mu.shape
         assert c == plan.hm
@@ -271,29 +222,37 @@ class CharmRun:
         self._hyper = (hyper_mu, hyper_sc)
         P = plan
         self.Cy = P.S * P.sc
-        mk = lambda c: torch.empty((self.M, c), dtype=torch.float32, device=self.dev)
-        self.A1, self.A2 = mk(P.NT * P.C1), mk(P.NT * P.C2)
-        self.MSL = mk(3 * self.Cy)
-        self.Yh, self.Ypre = mk(self.Cy), mk(self.Cy)
+        self.A1, self.A2 = self.wide(P.NT * P.C1), self.wide(P.NT * P.C2)
+        self.MSL = self.wide(3 * self.Cy)
+        self.Yh, self.Ypre = self.wide(self.Cy), self.wide(self.Cy)
         self.addr, ents, _ = P.fwd_packs()
         packs.ensure_fresh(ents)
-        self._bias = {}
 
-    # ---- views
-    def a1(self, slot, n=1):
-        return V(self.A1.data_ptr() + 4 * slot * self.p.C1, self.A1.shape[1], n * self.p.C1)
+    def wide(self, c: int) -> torch.Tensor:
+        return torch.empty((self.M, c), dtype=torch.float32, device=self.dev)
 
-    def a2(self, slot, n=1):
-        return V(self.A2.data_ptr() + 4 * slot * self.p.C2, self.A2.shape[1], n * self.p.C2)
+    # ---- views: one rule per buffer family; `of` = the backward's gradient buffer of the same layout instead
+    def a1(self, slot, n=1, of=None):
+        """first-layer slots [slot, slot + n)"""
+        return ops.view(self.A1 if of is None else of, slot * self.p.C1, n * self.p.C1)
 
-    def msl(self, which: int, i: int, n=1):
-        return V(self.MSL.data_ptr() + 4 * (which * self.Cy + i * self.p.sc), self.MSL.shape[1], n * self.p.sc)
+    def a2(self, slot, n=1, of=None):
+        """second-layer slots [slot, slot + n)"""
+        return ops.view(self.A2 if of is None else of, slot * self.p.C2, n * self.p.C2)
 
-    def yh(self, c0, c):
-        return V(self.Yh.data_ptr() + 4 * c0, self.Cy, c)
+    def msl(self, which: int, i: int, n=1, of=None):
+        """slices [i, i + n) of plane `which` of MSL (mu | sigma | lrp) -- or of G4 (d mu | d sigma | d lrp | dy)"""
+        return ops.view(self.MSL if of is None else of, which * self.Cy + i * self.p.sc, n * self.p.sc)
 
-    def yp(self, c0, c):
-        return V(self.Ypre.data_ptr() + 4 * c0, self.Cy, c)
+    def lat(self, buf: torch.Tensor, st):
+        """the slices of stage `st` (consecutive) of a latent-shaped buffer: Yh, Ypre, their gradient"""
+        return ops.view(buf, st[0] * self.p.sc, len(st) * self.p.sc)
+
+    def yh(self, *st):
+        return self.lat(self.Yh, st)
+
+    def yp(self, *st):
+        return self.lat(self.Ypre, st)
 
     def bias(self, kind, i, layer):
         return self.p.conv(kind, i, layer).bias.data_ptr()
@@ -318,11 +277,9 @@ class CharmRun:
 
     def hoist(self):
         P = self.p
-        self._conv([self.h_mu], [self.addr["hyp_mu"]], [self.a1(0, P.n_mu)], P.n_mu * P.C1, P.k1, wrows=P.n_mu * P.C1, wcols=P.hm,
-                   label="charm.hoist")
-        if self.with_scale:
-            self._conv([self.h_sc], [self.addr["hyp_sc"]], [self.a1(P.n_mu, P.n_sc)], P.n_sc * P.C1, P.k1, wrows=P.n_sc * P.C1,
-                       wcols=P.hm, label="charm.hoist")
+        for (name, lo, n), x in zip(P.halves(), (self.h_mu, self.h_sc)):
+            if x is not None:
+                self._conv([x], [self.addr[name]], [self.a1(lo, n)], n * P.C1, P.k1, wrows=n * P.C1, wcols=P.hm, label="charm.hoist")
 
     def _l23(self, trs, outs, label, ms=False):
         """second and third layer of the transforms `trs` -> outs (V into MSL)"""
@@ -362,26 +319,37 @@ class CharmRun:
         P = self.p
         if not P.ncons(k):
             return
-        x = self.yh(k * P.sc, P.sc)
         for half in (("mu", "sc") if self.with_scale else ("mu",)):
             lo, cons = P.consumers(k, half)
             n = len(cons)
-            self._conv([x], [self.addr[("sup_" + half, k)]], [self.a1(lo, n)], n * P.C1, P.k1, wrows=n * P.C1, wcols=P.sc, accum=True,
+            self._conv([self.yh(k)], [self.addr[("sup_" + half, k)]], [self.a1(lo, n)], n * P.C1, P.k1, wrows=n * P.C1, wcols=P.sc, accum=True,
                        label="charm.sup")
 
-    def quantize(self, st, y: Optional[V], noise: Optional[V], philox, lik_n, lik_q, bits_n, bits_q):
+    def gauss_operands(self, st, philox, bwd: Optional["CharmBackward"] = None):
+        """The GcDesc2 / GcIO pair of the Gaussian conditional over the channels of stage `st`.  Both directions read y, mu, sigma and the
+        noise source; the forward adds its outputs, the backward (`bwd` given) the gradients it reads and writes."""
+        P, Cy, i0 = self.p, self.Cy, st[0]
+        c0 = i0 * P.sc
+        y, noise = self.yv, self.nv
+        d = L.GcDesc2(N=self.n, HW=self.h * self.w, C=len(st) * P.sc, ldy=y.ld, ldmu=self.MSL.shape[1], ldsigma=self.MSL.shape[1],
+                      ldnoise=noise.ld if noise is not None else 0, Ctot=Cy, c0=c0, scale_bound=self.scale_bound,
+                      likelihood_bound=self.lik_bound)
+        io = L.GcIO(y=y.ptr + 4 * c0, mu=self.msl(0, i0).ptr, sigma=self.msl(1 if self.with_scale else 0, i0).ptr,
+                    noise=None if noise is None else noise.ptr + 4 * c0, philox=philox)
+        if bwd is None:
+            d.ldyhat = d.ldyhat2 = d.ldlik = Cy
+            io.yhat, io.yhat2 = self.yh(*st).ptr, self.yp(*st).ptr
+            io.lik_noisy, io.lik_quant = (None if t is None else t.data_ptr() + 4 * c0 for t in (self.lik_n, self.lik_q))
+            io.bits_noisy, io.bits_quant = ops._p(self.bits_n), ops._p(self.bits_q)
+        else:   # (G4 carries dy next to d mu | d sigma | d lrp so that the three gradients share one pixel stride)
+            d.ldgrad, d.lddyhat = bwd.G4.shape[1], Cy
+            io.gbits, io.dyhat = bwd.gbits.data_ptr(), bwd.dyv(*st).ptr
+            io.dmu, io.dsigma, io.dy = (bwd.g4(which, i0).ptr for which in (0, 1, 3))
+        return d, io
+
+    def quantize(self, st, philox):
         """Gaussian conditional over the channels of stage `st`: Yh = Ypre = round(y - mu) + mu, likelihoods, bit sums."""
-        P = self.p
-        c0, c = st[0] * P.sc, len(st) * P.sc
-        lib = L.load()
-        d = L.GcDesc2(N=self.n, HW=self.h * self.w, C=c, ldy=y.ld, ldmu=self.MSL.shape[1], ldsigma=self.MSL.shape[1], ldyhat=self.Cy,
-                      ldyhat2=self.Cy, ldnoise=noise.ld if noise is not None else 0, ldlik=self.Cy, ldgrad=0, lddyhat=0,
-                      Ctot=self.Cy, c0=c0, scale_bound=self.scale_bound, likelihood_bound=self.lik_bound)
-        io = L.GcIO(y=y.ptr + 4 * c0, mu=self.msl(0, st[0]).ptr, sigma=self.msl(1 if self.with_scale else 0, st[0]).ptr,
-                    noise=None if noise is None else noise.ptr + 4 * c0, philox=philox,
-                    yhat=self.yh(c0, c).ptr, yhat2=self.yp(c0, c).ptr,
-                    lik_noisy=None if lik_n is None else lik_n.data_ptr() + 4 * c0,
-                    lik_quant=None if lik_q is None else lik_q.data_ptr() + 4 * c0, bits_noisy=bits_n, bits_quant=bits_q)
+        d, io = self.gauss_operands(st, philox)
         HF.gauss_cond_fwd2(d, io, self.dev)
 
     def lrp(self, st):
@@ -390,37 +358,33 @@ class CharmRun:
         P = self.p
         lt = [("lrp", i) for i in st]
         sl = [self.a1(P.slot[t]) for t in lt]
-        self._conv([self.yh(i * P.sc, P.sc) for i in st], [self.addr[("lrp", i, "own")] for i in st], sl, P.C1, P.k1,
+        self._conv([self.yh(i) for i in st], [self.addr[("lrp", i, "own")] for i in st], sl, P.C1, P.k1,
                    wrows=P.C1, wcols=P.sc, biases=[self.bias("lrp", i, 0) for i in st], pres=sl, relu=True, label="charm.lrp.l1")
         self._l23(lt, [self.msl(2, i) for i in st], "charm.lrp")
-        c0, c = st[0] * P.sc, len(st) * P.sc
-        L.check(L.load().crdr_lrp(self.yp(c0, c).ptr, self.Cy, self.msl(2, st[0]).ptr, self.MSL.shape[1], self.yh(c0, c).ptr, self.Cy,
-                                  self.M, c, ops._stream()), "lrp")
+        L.check(L.load().crdr_lrp(self.yp(*st).ptr, self.Cy, self.msl(2, st[0]).ptr, self.MSL.shape[1], self.yh(*st).ptr, self.Cy,
+                                  self.M, len(st) * P.sc, ops._stream()), "lrp")
         if len(st) == 1:
             self.push_support(st[0])
 
     # ---- whole pass
-    def forward(self, y: torch.Tensor, noise: Optional[torch.Tensor], philox: Optional[int], scale_bound: float, lik_bound: float,
-                want_lik: bool, want_bits: bool):
+    def forward(self, y: torch.Tensor, noise: Optional[torch.Tensor], philox: Optional[int], want_lik: bool, want_bits: bool):
         y, ldy = ops.nhwc(y)
         self.y = y
-        self.yv = yv = V(y.data_ptr(), ldy, self.Cy)
-        self.nv = nv = None
+        self.yv = V(y.data_ptr(), ldy, self.Cy)
+        self.nv = None
         if noise is not None:
             noise, ldn = ops.nhwc(noise)
             self.noise = noise
-            self.nv = nv = V(noise.data_ptr(), ldn, self.Cy)
-        self.scale_bound, self.lik_bound = scale_bound, lik_bound
+            self.nv = V(noise.data_ptr(), ldn, self.Cy)
         noisy = noise is not None or philox is not None
-        mk = lambda: torch.empty((self.M, self.Cy), dtype=torch.float32, device=self.dev)
-        self.lik_n = mk() if (want_lik and noisy) else None
-        self.lik_q = mk() if want_lik else None
+        self.lik_n = self.wide(self.Cy) if (want_lik and noisy) else None
+        self.lik_q = self.wide(self.Cy) if want_lik else None
         self.bits_n = torch.zeros(self.n, dtype=torch.float32, device=self.dev) if (want_bits and noisy) else None
         self.bits_q = torch.zeros(self.n, dtype=torch.float32, device=self.dev) if want_bits else None
         self.hoist()
         for st in self.stages():
             self.mean_scale(st)
-            self.quantize(st, yv, nv, philox, self.lik_n, self.lik_q, ops._p(self.bits_n), ops._p(self.bits_q))
+            self.quantize(st, philox)
             self.lrp(st)
 
     def as_nchw(self, buf: torch.Tensor, c0: int = 0, c: Optional[int] = None) -> torch.Tensor:
@@ -431,136 +395,154 @@ class CharmRun:
 # ---------------------------------------------------------------------------------------------------------
 # backward
 # ---------------------------------------------------------------------------------------------------------
-_local_defer: Dict = {}
+class CharmBackward:
+    """The backward of one CharmRun, step by step: every stage method of the forward has its `_bwd` here and `run()` calls them in reverse
+    schedule order.  Owns the gradients of the wide buffers -- dA1 / dA2 (slots), G4 = d mu | d sigma | d lrp | dy, dY (d Yh, which
+    d Ypre shares: Yh = Ypre + ... is an identity path), dH (both hyper-prior halves); parameter gradients go straight into the (flat)
+    .grad slots."""
+
+    def __init__(self, run: CharmRun, dyhat: Optional[torch.Tensor], gbits: Optional[torch.Tensor], philox: Optional[int]):
+        self.r, self.p, self.philox = run, run.p, philox
+        P = run.p
+        self.baddr, bents, _ = P.bwd_packs()
+        packs.ensure_fresh(bents)
+        self.dA1, self.dA2 = run.wide(P.NT * P.C1), run.wide(P.NT * P.C2)
+        self.G4 = run.wide(4 * run.Cy)
+        self.dY = run.wide(run.Cy)
+        self.dH = run.wide(2 * P.hm)
+        if dyhat is None:
+            self.dY.zero_()
+        else:
+            run.as_nchw(self.dY).copy_(dyhat)
+        if gbits is None:
+            gbits = torch.zeros(run.n, dtype=torch.float32, device=run.dev)
+        self.gbits = gbits.contiguous()
+
+    # ---- views: the forward's, over the gradient buffers
+    def da1(self, slot, n=1):
+        return self.r.a1(slot, n, of=self.dA1)
+
+    def da2(self, slot, n=1):
+        return self.r.a2(slot, n, of=self.dA2)
+
+    def g4(self, which, i, n=1):
+        return self.r.msl(which, i, n, of=self.G4)
+
+    def dyv(self, *st):
+        return self.r.lat(self.dY, st)
+
+    def dh(self, half: int):
+        return ops.view(self.dH, half * self.p.hm, self.p.hm)
+
+    def wg(self, kind, i, layer):
+        return HF.grad_slot(self.p.conv(kind, i, layer).weight)
+
+    # ---- launches
+    def dgrad(self, xs, ws, ys, oc, k, wrows, wcols, masks=None, accum=False, label=""):
+        r = self.r
+        for a, b in _chunks(len(xs)):
+            ops.conv_group(r.n, r.h, r.w, xs[a:b], ws[a:b], ys[a:b], oc, k, k[0] // 2, True, wrows=wrows, wcols=wcols,
+                           masks=None if masks is None else masks[a:b], flags=L.EPI_ACCUM if accum else 0, device=r.dev, label=label)
+
+    def wgrad(self, ps, qs, gs, gi, gj, k, label=""):
+        r = self.r
+        for a, b in _chunks(len(ps)):
+            ops.wgrad_group(r.n, r.h, r.w, ps[a:b], qs[a:b], gs[a:b], gi, gj, k, k[0] // 2, device=r.dev, label=label)
+
+    def l32_bwd(self, trs, douts, label):
+        """third + second layer backward of transforms `trs` given the gradients of their outputs (V into G4):
+        leaves dz1 (masked) in dA1 slots, queues the weight gradients"""
+        P, r = self.p, self.r
+        sl = [P.slot[t] for t in trs]
+        d1, d2 = [self.da1(s) for s in sl], [self.da2(s) for s in sl]
+        a1, a2 = [r.a1(s) for s in sl], [r.a2(s) for s in sl]
+        self.dgrad(douts, [self.baddr[(k, i, "l3")] for k, i in trs], d2, P.C2, P.k3, P.C2, P.sc, masks=a2, label=label + ".l3")
+        self.wgrad(douts, a2, [(self.wg(k, i, 2).data_ptr(), 0) for k, i in trs], P.sc, P.C2, P.k3, label=label + ".l3")
+        self.dgrad(d2, [self.baddr[(k, i, "l2")] for k, i in trs], d1, P.C1, P.k2, P.C1, P.C2, masks=a1, label=label + ".l2")
+        self.wgrad(d2, a1, [(self.wg(k, i, 1).data_ptr(), 0) for k, i in trs], P.C2, P.C1, P.k2, label=label + ".l2")
+
+    def wide_l1_bwd(self, pack, lo, trs, x: V, dx: V, j0: int, label):
+        """Backward of ONE wide first-layer conv: input x = input channels [j0, j0 + x.c) of the transforms `trs`, which are the slots
+        [lo, lo + len(trs)); their (masked) first-layer gradients are final.  ONE K-concatenated input-gradient conv adds them to dx,
+        ONE slab launch yields the weight gradients (rows scattered to the parameters' columns by the batched reduce)."""
+        P, r = self.p, self.r
+        g = self.da1(lo, len(trs))
+        self.dgrad([g], [self.baddr[pack]], [dx], dx.c, P.k1, dx.c, g.c, accum=True, label=label)
+        gws = [self.wg(kind, i, 0) for kind, i in trs]
+        parts = [(idx * P.C1, P.C1, gw.data_ptr() + 4 * j0 * P.k1[0] * P.k1[1], gw.shape[1]) for idx, gw in enumerate(gws)]
+        ops.wgrad_split(r.n, r.h, r.w, g, x, parts, P.k1, P.k1[0] // 2, device=r.dev, label=label)
+
+    # ---- the forward's stages, backwards
+    def support_bwd(self, k: int):
+        """push_support: decoded slice k fed the first layer of every later transform"""
+        P = self.p
+        if not P.ncons(k):
+            return
+        for half in ("mu", "sc"):
+            lo, cons = P.consumers(k, half)
+            self.wide_l1_bwd(("sup_" + half, k), lo, cons, self.r.yh(k), self.dyv(k), P.hm + k * P.sc, "charm.sup")
+
+    def lrp_bwd(self, st):
+        P, r = self.p, self.r
+        if len(st) == 1:
+            self.support_bwd(st[0])
+        # Yh = Ypre + 0.5 tanh(lrp): d lrp
+        L.check(L.load().crdr_lrp_bwd(self.dyv(*st).ptr, r.Cy, r.msl(2, st[0]).ptr, r.MSL.shape[1], self.g4(2, st[0]).ptr, self.G4.shape[1],
+                                      r.M, len(st) * P.sc, ops._stream()), "lrp_bwd")
+        lt = [("lrp", i) for i in st]
+        self.l32_bwd(lt, [self.g4(2, i) for i in st], "charm.lrp")
+        # the slice's own pre-correction latent: d Ypre_i on top of d Yh_i
+        d1 = [self.da1(P.slot[t]) for t in lt]
+        self.dgrad(d1, [self.baddr[("lrp", i, "own")] for i in st], [self.dyv(i) for i in st], P.sc, P.k1, P.sc, P.C1, accum=True,
+                   label="charm.lrp.l1own")
+        t1 = P.k1[0] * P.k1[1]
+        gws = [self.wg("lrp", i, 0) for i in st]
+        self.wgrad(d1, [r.yp(i) for i in st], [(gw.data_ptr() + 4 * (P.hm + P.sup(i)) * t1, gw.shape[1]) for i, gw in zip(st, gws)],
+                   P.C1, P.sc, P.k1, label="charm.lrp.l1own")
+
+    def gauss_bwd(self, st):
+        d, io = self.r.gauss_operands(st, self.philox, bwd=self)
+        L.check(L.load().crdr_gauss_cond_bwd2(C.byref(d), C.byref(io), ops._stream()), "gauss_cond_bwd2")
+
+    def mean_scale_bwd(self, st):
+        P, r = self.p, self.r
+        trs = [(k, i) for k in ("mean", "scale") for i in st]
+        self.l32_bwd(trs, [self.g4(0 if k == "mean" else 1, i) for k, i in trs], "charm.ms")
+        if st[0] == 0:
+            d1 = [self.da1(P.slot[t]) for t in trs]
+            self.dgrad(d1, [self.baddr[(k, 0, "l1")] for k, _ in trs], [self.dh(0), self.dh(1)], P.hm, P.k1, P.hm, P.C1, label="charm.ms.l1")
+            self.wgrad(d1, [r.h_mu, r.h_sc], [(self.wg(k, 0, 0).data_ptr(), 0) for k, _ in trs], P.C1, P.hm, P.k1, label="charm.ms.l1")
+
+    def hoist_bwd(self):
+        P, r = self.p, self.r
+        for half, ((name, lo, n), x) in enumerate(zip(P.halves(), (r.h_mu, r.h_sc))):
+            self.wide_l1_bwd(name, lo, P.order[lo:lo + n], x, self.dh(half), 0, "charm.hoist")
+
+    def bias_grads(self):
+        """three column-sum passes over the wide gradient buffers"""
+        P, r = self.p, self.r
+        tb1, tb2, tb3 = P.bias_tables()
+        ops.colsum_scatter(ops.view(self.dA1, 0, self.dA1.shape[1]), r.M, P.C1, tb1, r.dev)
+        ops.colsum_scatter(ops.view(self.dA2, 0, self.dA2.shape[1]), r.M, P.C2, tb2, r.dev)
+        ops.colsum_scatter(ops.view(self.G4, 0, 3 * r.Cy), r.M, P.sc, tb3, r.dev)
+
+    def run(self):
+        """-> (dy, dhyper) as NCHW views"""
+        r = self.r
+        with ops.local_wgrad_defer(r.dev, ("charm-local", r.dev.index)):
+            for st in reversed(r.stages()):
+                self.lrp_bwd(st)
+                self.gauss_bwd(st)
+                self.mean_scale_bwd(st)
+            self.hoist_bwd()
+            self.bias_grads()
+        r._keep_bwd = (self.dA1, self.dA2, self.G4, self.dY, self.dH)
+        return r.as_nchw(self.G4, 3 * r.Cy), r.as_nchw(self.dH)
 
 
 def charm_backward(run: CharmRun, dyhat: Optional[torch.Tensor], gbits: Optional[torch.Tensor], philox: Optional[int]):
     """-> (dy, dhyper) as NCHW views; parameter gradients are accumulated straight into the (flat) .grad slots."""
-    P = run.p
-    lib = L.load()
-    dev, n, h, w, M, Cy = run.dev, run.n, run.h, run.w, run.M, run.Cy
-    S, ms, C1, C2, sc, hm, T = P.S, P.ms, P.C1, P.C2, P.sc, P.hm, P.T
-    baddr, bents, _ = P.bwd_packs()
-    packs.ensure_fresh(bents)
-    mk = lambda c, zero=False: (torch.zeros if zero else torch.empty)((M, c), dtype=torch.float32, device=dev)
-    dA1, dA2 = mk(P.NT * C1), mk(P.NT * C2)
-    G4 = mk(4 * Cy)            # dMU | dSG | dLR | dy (one pixel stride for the Gaussian-conditional backward)
-    dY = mk(Cy)
-    dH = mk(2 * hm)
-    if dyhat is None:
-        dY.zero_()
-    else:
-        dY.view(n, h, w, Cy).copy_(dyhat.permute(0, 2, 3, 1))
-    if gbits is None:
-        gbits = torch.zeros(n, dtype=torch.float32, device=dev)
-    gbits = gbits.contiguous()
-    da1 = lambda slot, k=1: V(dA1.data_ptr() + 4 * slot * C1, dA1.shape[1], k * C1)
-    da2 = lambda slot, k=1: V(dA2.data_ptr() + 4 * slot * C2, dA2.shape[1], k * C2)
-    g4 = lambda which, i, k=1: V(G4.data_ptr() + 4 * (which * Cy + i * sc), 4 * Cy, k * sc)
-    dyv = lambda c0, c: V(dY.data_ptr() + 4 * c0, Cy, c)
-    pad1, pad2, pad3 = P.k1[0] // 2, P.k2[0] // 2, P.k3[0] // 2
-    t1 = P.k1[0] * P.k1[1]
-
-    def wg(kind, i, layer):
-        return HF.grad_slot(P.conv(kind, i, layer).weight)
-
-    def dgrad(xs, ws, ys, oc, k, wrows, wcols, masks=None, accum=False, label=""):
-        for a, b in _chunks(len(xs)):
-            ops.conv_group(n, h, w, xs[a:b], ws[a:b], ys[a:b], oc, k, k[0] // 2, True, wrows=wrows, wcols=wcols,
-                           masks=None if masks is None else masks[a:b], flags=L.EPI_ACCUM if accum else 0, device=dev, label=label)
-
-    def wgrad(ps, qs, gs, gi, gj, k, label=""):
-        for a, b in _chunks(len(ps)):
-            ops.wgrad_group(n, h, w, ps[a:b], qs[a:b], gs[a:b], gi, gj, k, k[0] // 2, device=dev, label=label)
-
-    prev_defer = ops.WGRAD_DEFER
-    local = prev_defer is None or prev_defer.device != dev
-    if local:
-        d = _local_defer.get(dev)
-        if d is None:
-            d = _local_defer[dev] = ops.DeferredWgrad(dev, arena_bytes=256 << 20)
-        ops.WGRAD_DEFER = d
-    try:
-        def l32_bwd(trs, douts, label):
-            """third + second layer backward of transforms `trs` given the gradients of their outputs (V into G4):
-            leaves dz1 (masked) in dA1 slots, queues the weight gradients"""
-            sl = [P.slot[t] for t in trs]
-            dgrad(douts, [baddr[(k, i, "l3")] for k, i in trs], [da2(s) for s in sl], C2, P.k3, C2, sc,
-                  masks=[run.a2(s) for s in sl], label=label + ".l3")
-            wgrad(douts, [run.a2(s) for s in sl], [(wg(k, i, 2).data_ptr(), 0) for k, i in trs], sc, C2, P.k3, label=label + ".l3")
-            dgrad([da2(s) for s in sl], [baddr[(k, i, "l2")] for k, i in trs], [da1(s) for s in sl], C1, P.k2, C1, C2,
-                  masks=[run.a1(s) for s in sl], label=label + ".l2")
-            wgrad([da2(s) for s in sl], [run.a1(s) for s in sl], [(wg(k, i, 1).data_ptr(), 0) for k, i in trs], C2, C1, P.k2,
-                  label=label + ".l2")
-
-        def gc_bwd(st):
-            c0, c = st[0] * sc, len(st) * sc
-            d = L.GcDesc2(N=n, HW=h * w, C=c, ldy=run.yv.ld, ldmu=3 * Cy, ldsigma=3 * Cy,
-                          ldyhat=0, ldyhat2=0, ldnoise=0 if run.nv is None else run.nv.ld, ldlik=0, ldgrad=4 * Cy, lddyhat=Cy,
-                          Ctot=Cy, c0=c0, scale_bound=run.scale_bound, likelihood_bound=run.lik_bound)
-            io = L.GcIO(y=run.yv.ptr + 4 * c0, mu=run.msl(0, st[0]).ptr, sigma=run.msl(1, st[0]).ptr,
-                        noise=None if run.nv is None else run.nv.ptr + 4 * c0, philox=philox, gbits=gbits.data_ptr(),
-                        dyhat=dyv(c0, c).ptr, dy=g4(3, st[0]).ptr, dmu=g4(0, st[0]).ptr, dsigma=g4(1, st[0]).ptr)
-            L.check(lib.crdr_gauss_cond_bwd2(C.byref(d), C.byref(io), ops._stream()), "gauss_cond_bwd2")
-
-        for st in reversed(run.stages()):
-            c0, c = st[0] * sc, len(st) * sc
-            lt = [("lrp", i) for i in st]
-            if len(st) == 1 and P.ncons(st[0]):
-                # decoded slice k fed the first layer of every later transform: their (masked) first-layer gradients are final by
-                # now -- ONE K-concatenated input-gradient conv per half adds them to d Yh_k, ONE slab launch per half yields the
-                # weight gradients of those parts (rows scattered to the parameters' support columns by the batched reduce)
-                k = st[0]
-                for half in ("mu", "sc"):
-                    lo, cons = P.consumers(k, half)
-                    nc = len(cons)
-                    dgrad([da1(lo, nc)], [baddr[("sup_" + half, k)]], [dyv(k * sc, sc)], sc, P.k1, sc, nc * C1, accum=True, label="charm.sup")
-                    parts = []
-                    for idx, (kind, j) in enumerate(cons):
-                        gw = wg(kind, j, 0)
-                        parts.append((idx * C1, C1, gw.data_ptr() + 4 * (hm + k * sc) * t1, gw.shape[1]))
-                    ops.wgrad_split(n, h, w, da1(lo, nc), run.yh(k * sc, sc), parts, P.k1, pad1, device=dev, label="charm.sup")
-            # Yh = Ypre + 0.5 tanh(lrp): d lrp
-            L.check(lib.crdr_lrp_bwd(dyv(c0, c).ptr, Cy, run.msl(2, st[0]).ptr, 3 * Cy, g4(2, st[0]).ptr, 4 * Cy, M, c, ops._stream()),
-                    "lrp_bwd")
-            l32_bwd(lt, [g4(2, i) for i in st], "charm.lrp")
-            # the slice's own pre-correction latent: d Ypre_i on top of d Yh_i (Yh = Ypre + ...: the identity path shares dY)
-            dgrad([da1(P.slot[t]) for t in lt], [baddr[("lrp", i, "own")] for i in st], [dyv(i * sc, sc) for i in st], sc, P.k1, sc, C1,
-                  accum=True, label="charm.lrp.l1own")
-            wgrad([da1(P.slot[t]) for t in lt], [run.yp(i * sc, sc) for i in st],
-                  [(wg("lrp", i, 0).data_ptr() + 4 * (hm + P.sup(i)) * t1, wg("lrp", i, 0).shape[1]) for i in st], C1, sc, P.k1,
-                  label="charm.lrp.l1own")
-            gc_bwd(st)
-            trs = [(k, i) for k in ("mean", "scale") for i in st]
-            l32_bwd(trs, [g4(0 if k == "mean" else 1, i) for k, i in trs], "charm.ms")
-            if st[0] == 0:
-                dgrad([da1(P.slot[("mean", 0)]), da1(P.slot[("scale", 0)])], [baddr[("mean", 0, "l1")], baddr[("scale", 0, "l1")]],
-                      [V(dH.data_ptr(), 2 * hm, hm), V(dH.data_ptr() + 4 * hm, 2 * hm, hm)], hm, P.k1, hm, C1, label="charm.ms.l1")
-                wgrad([da1(P.slot[("mean", 0)]), da1(P.slot[("scale", 0)])], [run.h_mu, run.h_sc],
-                      [(wg("mean", 0, 0).data_ptr(), 0), (wg("scale", 0, 0).data_ptr(), 0)], C1, hm, P.k1, label="charm.ms.l1")
-        # hoisted hyper-prior parts
-        for name, lo, cnt, hv, c0 in (("hyp_mu", 0, P.n_mu, run.h_mu, 0), ("hyp_sc", P.n_mu, P.n_sc, run.h_sc, hm)):
-            dgrad([da1(lo, cnt)], [baddr[name]], [V(dH.data_ptr() + 4 * c0, 2 * hm, hm)], hm, P.k1, hm, cnt * C1, accum=True,
-                  label="charm.hoist")
-            parts = []
-            for k in range(cnt):
-                kind, i = P.order[lo + k]
-                gw = wg(kind, i, 0)
-                parts.append((k * C1, C1, gw.data_ptr(), gw.shape[1]))
-            ops.wgrad_split(n, h, w, da1(lo, cnt), hv, parts, P.k1, pad1, device=dev, label="charm.hoist")
-        # bias gradients: three column-sum passes
-        tb1, tb2, tb3 = P.bias_tables()
-        ops.colsum_scatter(V(dA1.data_ptr(), dA1.shape[1], dA1.shape[1]), M, C1, tb1, dev)
-        ops.colsum_scatter(V(dA2.data_ptr(), dA2.shape[1], dA2.shape[1]), M, C2, tb2, dev)
-        ops.colsum_scatter(V(G4.data_ptr(), 4 * Cy, 3 * Cy), M, sc, tb3, dev)
-        if local:
-            ops.WGRAD_DEFER.flush(("charm-local", dev.index))
-    finally:
-        ops.WGRAD_DEFER = prev_defer
-    run._keep_bwd = (dA1, dA2, G4, dY, dH)
-    dy = G4.view(n, h, w, 4 * Cy).permute(0, 3, 1, 2)[:, 3 * Cy:]
-    dhyper = dH.view(n, h, w, 2 * hm).permute(0, 3, 1, 2)
-    return dy, dhyper
+    return CharmBackward(run, dyhat, gbits, philox).run()
 
 
 class _CharmFn(torch.autograd.Function):
@@ -570,7 +552,7 @@ class _CharmFn(torch.autograd.Function):
     def forward(ctx, y, hyper_out, noise, module, philox_state, scale_bound, lik_bound, want_lik, is_train):
         plan = plan_for(module)
         h_mu, h_sc = torch.chunk(hyper_out, 2, dim=1)
-        run = CharmRun(plan, h_mu, h_sc)
+        run = CharmRun(plan, h_mu, h_sc, scale_bound, lik_bound)
         ph = None
         if is_train and noise is None:
             ph_call = torch.empty(2, dtype=torch.int64, device=y.device)
@@ -578,7 +560,7 @@ class _CharmFn(torch.autograd.Function):
             L.check(L.load().crdr_philox_fork(philox_state.data_ptr(), ph_call.data_ptr(), inc, ops._stream()), "philox_fork")
             ph = ph_call.data_ptr()
             ctx.ph_call = ph_call
-        run.forward(y, noise if is_train else None, ph, scale_bound, lik_bound, want_lik, True)
+        run.forward(y, noise if is_train else None, ph, want_lik, True)
         ctx.run, ctx.ph = run, ph
         if ops.RELU_MASK_SINK is not None and any(ctx.needs_input_grad):   # (test hook: the activations charm_backward takes its ReLU masks from)
             for (kind, i), slot in plan.slot.items():
@@ -613,6 +595,6 @@ def charm_forward(module, y, hyper_out, noise, philox_state, scale_bound, lik_bo
 def charm_reconstruct(module, y, hyper_mu, scale_bound, lik_bound) -> CharmRun:
     """y_hat only (the no-grad high-rate pass of stage 3): no scale transforms, no likelihoods.  Returns the run (y_hat =
     run.as_nchw(run.Yh))."""
-    run = CharmRun(plan_for(module), hyper_mu, None)
-    run.forward(y, None, None, float(scale_bound), float(lik_bound), False, False)
+    run = CharmRun(plan_for(module), hyper_mu, None, scale_bound, lik_bound)
+    run.forward(y, None, None, False, False)
     return run

@@ -5,6 +5,7 @@ to the kernels in place through its pixel stride (`ld`).  All arithmetic happens
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional, Tuple
@@ -585,6 +586,33 @@ def reduce_jobs_now(jobs, device) -> None:
 
 
 WGRAD_DEFER: Optional[DeferredWgrad] = None  # set by a trainer; every backward must then be followed by flush_wgrads()
+
+
+_local_defers = {}
+
+
+@contextlib.contextmanager
+def local_wgrad_defer(device, site):
+    """Around a hand-written backward whose slab launches defer their reductions.  A trainer already defers on this device: nothing to do,
+    the trainer flushes.  Otherwise the device's private DeferredWgrad stands in: flushed at `site` on the way out, its pending jobs
+    dropped when the backward raises (the next one must not reduce stale slabs); the previous value is restored either way."""
+    global WGRAD_DEFER
+    prev = WGRAD_DEFER
+    if prev is not None and prev.device == device:
+        yield
+        return
+    d = _local_defers.get(device)
+    if d is None:
+        d = _local_defers[device] = DeferredWgrad(device, arena_bytes=256 << 20)
+    WGRAD_DEFER = d
+    try:
+        yield
+        d.flush(site)
+    except BaseException:
+        d.drop()
+        raise
+    finally:
+        WGRAD_DEFER = prev
 
 
 def flush_wgrads(key=None) -> None:

@@ -144,8 +144,7 @@ class Minnen20CharmContextModel(BaseContextModel):
         dec = rans.RansDecoder()
         dec.set_stream(y_str)
         h_mu, h_sc = torch.chunk(hyper_out, 2, dim=1)
-        run = charm.CharmRun(charm.plan_for(self), h_mu, h_sc)
-        run.scale_bound, run.lik_bound = entropy_model_y.scale_bound, entropy_model_y.likelihood_bound
+        run = charm.CharmRun(charm.plan_for(self), h_mu, h_sc, entropy_model_y.scale_bound, entropy_model_y.likelihood_bound)
         run.hoist()
         sc = self.slice_ch
         mu_all, sg_all = run.as_nchw(run.MSL, 0, run.Cy), run.as_nchw(run.MSL, run.Cy, run.Cy)

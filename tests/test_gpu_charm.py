@@ -296,3 +296,137 @@ def test_charm_philox_training_noise():
     assert torch.equal(b1, b2) and torch.equal(gy1, gy2) and torch.equal(gh1, gh2)
     b3, _, _ = run(None)
     assert not torch.equal(b1, b3), "two training passes drew the same noise"
+
+
+@pytest.mark.parametrize("max_support, ms, tail", [(2, 2, 2), (-1, 4, 0), (3, 4, 0)])
+def test_charm_pack_layout_is_plain_indexing(max_support, ms, tail):
+    """The three schedule shapes (a two-slice tail; no tail; a one-slice tail, which the plan folds into the sequential part): every forward
+    pack is pack[t][blk * I + i][j] = w[i, j0 + j, t // kw, t % kw] of its blocks, exactly, every input-gradient pack its transpose, and
+    both directions know the same keys.  (Every channel count is a multiple of 32: the packs have no padding.)"""
+    from crdr_amd.hip import charm, packs
+    from crdr_amd.models.subnet.context_model.minnen20_charm_context_model import Minnen20CharmContextModel
+    S, sc, hm = 4, 32, 64
+    m = Minnen20CharmContextModel(num_slices=S, bottleneck_y=S * sc, hyper_out_ch=2 * hm, max_support_slices=max_support)
+    seed_module(m, "context_model.")
+    m.to(dev())
+    plan = charm.plan_for(m)
+    assert (plan.ms, plan.T) == (ms, tail)
+    (faddr, fents, fbufs), (baddr, bents, bbufs) = plan.fwd_packs(), plan.bwd_packs()
+    packs.ensure_fresh(fents)
+    packs.ensure_fresh(bents)
+    layout = list(plan.pack_layout())
+    keys = [key for key, _, _ in layout]
+    assert len(set(keys)) == len(keys) == len(fbufs) == len(bbufs)
+    assert set(faddr) == set(baddr) == set(keys)
+    # the keys and the support rule, written down independently of the enumeration
+    want = {"hyp_mu", "hyp_sc"} | {(kind, i, l) for kind in ("mean", "scale", "lrp") for i in range(S) for l in ("l2", "l3")}
+    want |= {("mean", 0, "l1"), ("scale", 0, "l1")} | {("lrp", i, "own") for i in range(S)}
+    want |= {("sup_" + half, k) for half in ("mu", "sc") for k in range(min(ms, S - 1))}
+    assert set(keys) == want
+    by_key = {key: blocks for key, _, blocks in layout}
+    for i in range(S):
+        (w, j0, j1), = by_key[("lrp", i, "own")]
+        assert w is plan.conv("lrp", i, 0).weight and (j0, j1) == (hm + sc * min(i, ms), w.shape[1])
+    for k in range(min(ms, S - 1)):
+        for half, per_slice in (("mu", 2), ("sc", 1)):
+            blocks = by_key[("sup_" + half, k)]
+            assert len(blocks) == per_slice * (S - 1 - k) and all((j0, j1) == (hm + k * sc, hm + (k + 1) * sc) for _, j0, j1 in blocks)
+    for (key, taps, blocks), fbuf, bbuf in zip(layout, fbufs, bbufs):
+        assert faddr[key] == fbuf.data_ptr() and baddr[key] == bbuf.data_ptr()
+        ref = torch.cat([w.detach().cpu()[:, j0:j1].reshape(w.shape[0], j1 - j0, taps).permute(2, 0, 1) for w, j0, j1 in blocks], dim=1)
+        assert blocks[0][0].shape[2] * blocks[0][0].shape[3] == taps
+        assert torch.equal(fbuf.cpu(), ref), f"forward pack {key}"
+        assert torch.equal(bbuf.cpu(), ref.transpose(1, 2)), f"input-gradient pack {key}"
+
+
+def _queue_one_wgrad():
+    """one ops.wgrad_group job (2x8x8, 64 -> 32, 3x3) on the active deferral -> the tensors it reads and writes (to be kept alive)"""
+    from crdr_amd.hip import ops
+    from crdr_amd.hip.ops import view
+    n, h, w, ci, co = 2, 8, 8, 64, 32
+    X, DY = wide(n * h * w, ci, 0.5), wide(n * h * w, co, 0.25)
+    g = torch.zeros((co, ci, 3, 3), dtype=torch.float32, device=dev())
+    ops.wgrad_group(n, h, w, [view(DY, 0, co)], [view(X, 0, ci)], [(g.data_ptr(), 0)], co, ci, (3, 3), 1, device=dev())
+    return X, DY, g
+
+
+def test_local_wgrad_defer_scope(monkeypatch):
+    """ops.local_wgrad_defer: a private deferral when none is active on the device (flushed on the way out), nothing when one is (its
+    owner flushes), and a raise inside a private scope drops what was queued; the previous value comes back in every case."""
+    import types
+    from crdr_amd.hip import ops
+    site = ("test-local", 0)
+    # nothing set
+    monkeypatch.setattr(ops, "WGRAD_DEFER", None)
+    with ops.local_wgrad_defer(dev(), site):
+        private = ops.WGRAD_DEFER
+        assert isinstance(private, ops.DeferredWgrad) and private.device == dev()
+        keep = _queue_one_wgrad()
+        assert private.pending() == 1
+    assert ops.WGRAD_DEFER is None and private.pending() == 0
+    assert torch.all(keep[2][:, :, 1, 1] == 2 * 8 * 8 * 0.5 * 0.25), "the scope did not flush its job"   # (centre tap: every pixel pair)
+    # a deferral already active on the device: left in place, not flushed
+    mine = ops.DeferredWgrad(dev(), arena_bytes=64 << 20)
+    monkeypatch.setattr(ops, "WGRAD_DEFER", mine)
+    with ops.local_wgrad_defer(dev(), site):
+        assert ops.WGRAD_DEFER is mine
+        keep = _queue_one_wgrad()
+    assert ops.WGRAD_DEFER is mine and mine.pending() == 1 and private.pending() == 0
+    mine.drop()
+    # an exception inside a private scope (the previous value: a deferral of another device)
+    other = types.SimpleNamespace(device=torch.device("cpu"))
+    monkeypatch.setattr(ops, "WGRAD_DEFER", other)
+    with pytest.raises(RuntimeError, match="inside the scope"):
+        with ops.local_wgrad_defer(dev(), site):
+            assert ops.WGRAD_DEFER is private
+            keep = _queue_one_wgrad()
+            assert private.pending() == 1
+            raise RuntimeError("inside the scope")
+    assert ops.WGRAD_DEFER is other and private.pending() == 0
+    torch.cuda.synchronize()
+
+
+def test_chain_backward_raise_does_not_poison_the_next(monkeypatch):
+    """A chain backward that raises (a Python exception at its column-sum flush, after every launch was issued and every reduction queued)
+    leaves nothing behind: the next backward of the same ChainSpec gives the gradients of an undisturbed run, bit for bit.
+    One residual unit of two 3x3 convs 32 -> 32 at 1x32x6x6."""
+    from crdr_amd.hip import chain as CH, ops
+    from crdr_amd.models.layer.hip_layers import HipConv2d
+    convs = [HipConv2d(32, 32, 3, padding=1) for _ in range(2)]
+    for k, cv in enumerate(convs):
+        cv.load_state_dict({"weight": seeded_tensor(f"poison.{k}.weight", cv.weight.shape), "bias": seeded_tensor(f"poison.{k}.bias", cv.bias.shape)})
+        cv.to(dev())
+    spec = CH.ChainSpec([[CH.Unit([CH.Layer(convs[0], "relu"), CH.Layer(convs[1])], True)]], name="poison")
+    params = [p for cv in convs for p in (cv.weight, cv.bias)]
+    x, cot = seeded_input("poison.x", (1, 32, 6, 6)), seeded_input("poison.cot", (1, 32, 6, 6)).to(dev())
+    monkeypatch.setattr(ops, "WGRAD_DEFER", None)
+
+    def backward():
+        for p in params:
+            p.grad = None
+        xd = nhwc(x).requires_grad_(True)
+        y, = CH.run_chain(xd, spec)
+        (y * cot).sum().backward()
+        return [xd.grad.clone()] + [p.grad.clone() for p in params]
+
+    class FailingFlush:
+        def __init__(self, q):
+            self.q = q
+
+        def __getattr__(self, name):
+            return getattr(self.q, name)
+
+        def flush(self, key):
+            assert self.q.jobs and ops.WGRAD_DEFER.pending(), "the raise must come with reductions pending"
+            raise RuntimeError("poisoned flush")
+
+    want = backward()
+    real = ops.colsum_queue
+    with monkeypatch.context() as mp:
+        mp.setattr(ops, "colsum_queue", lambda device: FailingFlush(real(device)))
+        with pytest.raises(RuntimeError, match="poisoned flush"):
+            backward()
+    assert ops.WGRAD_DEFER is None and not real(dev()).jobs
+    got = backward()
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
