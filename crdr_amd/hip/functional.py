@@ -676,6 +676,59 @@ def bce_diff_sum(p, q, target: float):
     return _PairSum.apply(p, q, "bce_diff_sum", float(target))
 
 
+GAN_BCE, GAN_HINGE_D, GAN_HINGE_G = 0, 1, 2   # crdr_gan_loss_desc.kind
+
+
+class _GanLossSum(torch.autograd.Function):
+    """(p, q, mask) -> one float: sum_i mask_i l(p_i - r_i) of crdr_gan_loss_fwd, r = q (paired), mean(q) (centred) or 0 (q is None).
+    Operands are flattened like _PairSum's bce_diff_sum: each in its own contiguous order.  The mask gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, p, q, mask, kind, target, sgn, center):
+        lib = L.load()
+        fp = p.contiguous().reshape(-1)
+        fq = None if q is None else q.contiguous().reshape(-1)
+        fm = None if mask is None else mask.expand_as(p).contiguous().reshape(-1)
+        if fq is not None and not center and fq.numel() != fp.numel():
+            raise ValueError(f"gan_loss_sum: paired operands of {fp.numel()} and {fq.numel()} elements")
+        if center and fq is None:
+            raise ValueError("gan_loss_sum: center=True needs q")
+        for t in (fp, fq, fm):
+            if t is not None and (t.dtype != torch.float32 or t.device != p.device or not t.is_cuda):
+                raise ValueError("gan_loss_sum: operands are float32 tensors on one GPU")
+        d = L.GanLossDesc(n=fp.numel(), nq=0 if fq is None else fq.numel(), kind=int(kind), center=int(bool(center)),
+                          target=float(target), sgn=float(sgn))
+        out = torch.empty(1, dtype=torch.float32, device=p.device)
+        stats = torch.empty(2, dtype=torch.float32, device=p.device)
+        ws, wsn = ops.workspace(lib.crdr_gan_loss_workspace(d.n, d.nq), p.device)
+        L.check(lib.crdr_gan_loss_fwd(C.byref(d), fp.data_ptr(), ops._p(fq), ops._p(fm), out.data_ptr(), stats.data_ptr(), ws, wsn,
+                                      ops._stream()), "gan_loss_fwd")
+        ctx.desc, ctx.has_q, ctx.has_mask = d, fq is not None, fm is not None
+        ctx.shapes = (p.shape, None if q is None else q.shape)
+        ctx.save_for_backward(fp, stats, *([fq] if fq is not None else []), *([fm] if fm is not None else []))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.load()
+        fp, stats, *rest = ctx.saved_tensors
+        fq = rest.pop(0) if ctx.has_q else None
+        fm = rest.pop(0) if ctx.has_mask else None
+        d = ctx.desc
+        dp = torch.empty_like(fp) if ctx.needs_input_grad[0] else None
+        dq = torch.empty_like(fq) if (fq is not None and ctx.needs_input_grad[1]) else None
+        ws, wsn = ops.workspace(lib.crdr_gan_loss_workspace(d.n, d.nq), fp.device)
+        L.check(lib.crdr_gan_loss_bwd(C.byref(d), fp.data_ptr(), ops._p(fq), ops._p(fm), stats.data_ptr(), g.contiguous().data_ptr(), 1.0,
+                                      ops._p(dp), ops._p(dq), ws, wsn, ops._stream()), "gan_loss_bwd")
+        return (_unflat(dp, ctx.shapes[0], None), _unflat(dq, ctx.shapes[1], None), None, None, None, None, None)
+
+
+def gan_loss_sum(p, q=None, *, kind: int, target: float = 0.0, sgn: float = 1.0, center: bool = False, mask=None):
+    """sum_i mask_i l(p_i - r_i): kind GAN_BCE (BCEWithLogits against `target`), GAN_HINGE_D (max(1 - sgn x, 0)) or GAN_HINGE_G (-x);
+    r = q elementwise, mean(q) with center=True (q of any size), 0 without q.  Gradients flow to p and to q."""
+    return _GanLossSum.apply(p, q, mask, int(kind), float(target), float(sgn), bool(center))
+
+
 class _MaxPool3s2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

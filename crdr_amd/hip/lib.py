@@ -75,6 +75,10 @@ class ChannelNormDesc(C.Structure):
         ("slope", C.c_float), ("eps", C.c_float)]
 
 
+class GanLossDesc(C.Structure):  # mirrors struct crdr_gan_loss_desc
+    _fields_ = [("n", C.c_int64), ("nq", C.c_int64), ("kind", C.c_int32), ("center", C.c_int32), ("target", C.c_float), ("sgn", C.c_float)]
+
+
 class GcDesc2(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("N", "HW", "C", "ldy", "ldmu", "ldsigma", "ldyhat", "ldyhat2", "ldnoise", "ldlik",
                                          "ldgrad", "lddyhat", "Ctot", "c0")] + [
@@ -185,6 +189,9 @@ SIGNATURES = {
     "crdr_sqdiff_bwd": (_I, [_P, _P, _I64, _P, _F, _P, _P, _P]),
     "crdr_bce_diff_sum": (_I, [_P, _P, _I64, _F, _P, _P, _SZ, _P]),
     "crdr_bce_diff_bwd": (_I, [_P, _P, _I64, _F, _P, _F, _P, _P, _P]),
+    "crdr_gan_loss_workspace": (_SZ, [_I64, _I64]),
+    "crdr_gan_loss_fwd": (_I, [C.POINTER(GanLossDesc), _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "crdr_gan_loss_bwd": (_I, [C.POINTER(GanLossDesc), _P, _P, _P, _P, _P, _F, _P, _P, _P, _SZ, _P]),
     "crdr_l1_sum": (_I, [_P, _P, _I64, _P, _P, _SZ, _P]),
     "crdr_l1_bwd": (_I, [_P, _P, _I64, _P, _F, _P, _P, _P]),
     "crdr_msssim_workspace": (_SZ, [_I, _I, _I, _I]),

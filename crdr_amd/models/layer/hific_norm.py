@@ -65,10 +65,16 @@ def channel_norm_bwd(x, ldx, gamma, beta, stats, dy, *, eps, act, slope, dgamma=
     return dx
 
 
+def _aligned(t):
+    """`t`, or a copy of it where `t` does not start on a 16-byte boundary: a parameter that an optimiser laid out in its flat buffer
+    behind one with an odd element count (the RGB bias of a decoder's last conv) -- the kernels load gamma / beta four at a time"""
+    return t if t is None or t.data_ptr() % 16 == 0 else t.detach().clone()
+
+
 class _ChannelNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, res, eps: float, act, slope: float):
-        y, stats, x, ldx = channel_norm_fwd(x, gamma, beta, eps=eps, act=act, slope=slope, res=res)
+        y, stats, x, ldx = channel_norm_fwd(x, _aligned(gamma), _aligned(beta), eps=eps, act=act, slope=slope, res=res)
         ctx.save_for_backward(x, gamma, beta, stats)
         ctx.cfg = (ldx, eps, act, slope, res is not None)
         return y
@@ -80,7 +86,13 @@ class _ChannelNormFn(torch.autograd.Function):
         needs = ctx.needs_input_grad
         gg = HF.grad_slot(gamma) if (gamma is not None and needs[1]) else None
         gb = HF.grad_slot(beta) if (beta is not None and needs[2]) else None
-        dx = channel_norm_bwd(x, ldx, gamma, beta, stats, dy, eps=eps, act=act, slope=slope, dgamma=gg, dbeta=gb)
+        # (a gradient slot off the 16-byte grid -- see _aligned -- is accumulated into through a zeroed, aligned stand-in)
+        sg, sb = (None if g is None or g.data_ptr() % 16 == 0 else torch.zeros(g.shape, dtype=g.dtype, device=g.device) for g in (gg, gb))
+        dx = channel_norm_bwd(x, ldx, _aligned(gamma), _aligned(beta), stats, dy, eps=eps, act=act, slope=slope,
+                              dgamma=gg if sg is None else sg, dbeta=gb if sb is None else sb)
+        for slot, stand_in in ((gg, sg), (gb, sb)):
+            if stand_in is not None:
+                slot.add_(stand_in)
         return dx, None, None, (dy if has_res else None), None, None, None
 
 

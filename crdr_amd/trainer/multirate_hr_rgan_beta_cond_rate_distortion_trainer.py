@@ -17,44 +17,23 @@ from __future__ import annotations
 
 from typing import Dict
 
-import numpy as np
 import torch
 
 from crdr_amd.hip import chain as _chain
 from crdr_amd.utils.registry import TRAINER_REGISTRY
 
 from . import dist as D
+from .beta_conditions import BetaConditions
 from .multirate_hr_rgan_rate_distortion_trainer import MultirateHighRateRGANRateDistortionTrainer
 
 
 @TRAINER_REGISTRY.register()
-class MultirateBetaCondHrrGanRateDistortionTrainer(MultirateHighRateRGANRateDistortionTrainer):
+class MultirateBetaCondHrrGanRateDistortionTrainer(BetaConditions, MultirateHighRateRGANRateDistortionTrainer):
     def __init__(self, opt, relative_score_rate_delta=1) -> None:
         super().__init__(opt, relative_score_rate_delta)
         # `reuse_d_forward` (default on): the discriminator phase takes D(x_hat) from the generator phase's forward instead of evaluating it again
         self.reuse_d_forward = bool(opt.get("reuse_d_forward", __import__("os").environ.get("CRDR_REUSE_D_FORWARD", "1") != "0"))
-        seed = int(opt.get("cond_seed", 0))
-        self._q_gen = torch.Generator().manual_seed(seed)
-        self._b_rng = np.random.default_rng(seed)
-
-    def _conditions(self, data_dict: Dict):
-        """Draw (q, beta) for this iteration (reference: one draw per batch, interpca_hyperprior_model.py:43-45 and
-        beta_cond_interpca_hyperprior_model.py:41-46).  q selects the graph; beta enters through device buffers."""
-        q = data_dict.get("rate_ind")
-        if q is None:
-            q = torch.randint(self.rate_level, (1,), generator=self._q_gen) if D.is_dist() else self.comp_model.sample_rate_ind()
-        q = int(q.item()) if isinstance(q, torch.Tensor) else int(q)
-        beta = data_dict.get("beta")
-        if beta is None:
-            beta = (self.comp_model.max_beta * (float(self._b_rng.integers(0, 101)) / 100.0)) if D.is_dist() else self.comp_model.sample_beta()
-        beta = float(beta)
-        dec = self.comp_model.decoder
-        if getattr(dec, "static_embed", None) is None:
-            dec.static_embed = torch.zeros(1, dec.embed.embed(0.0).shape[1], 1, 1, device=self.device)
-            self._beta_t = torch.zeros(1, device=self.device)
-        dec.static_embed.copy_(dec.embed.embed(beta).reshape(dec.static_embed.shape))
-        self._beta_t.fill_(beta)
-        return {"rate_ind": q, "beta": beta}, ("s3", q)
+        self._init_conditions(opt)   # the (q, beta) draw: beta_conditions.py
 
     # ------------------------------------------------------------------ G phase: forward, losses, backward
     def _g_forward(self, real, cond: Dict, noise, current_iter: int) -> Dict:

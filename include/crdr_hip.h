@@ -608,6 +608,30 @@ int crdr_bce_diff_sum(const float* p, const float* q, int64_t n, float target, f
                       crdr_stream_t s);
 int crdr_bce_diff_bwd(const float* p, const float* q, int64_t n, float target, const float* g, float gscale, float* dp,
                       float* dq, crdr_stream_t s);
+/* The single-rate GAN objectives on discriminator logits, summed (the caller divides by n for the mean):
+ *   x_i = p_i - r_i;  r_i = q_i (paired: q has n elements, center = 0) | mean(q) (centred: q has nq elements, center = 1; the
+ *   relativistic-average form) | 0 (q == NULL)
+ *   kind 0: l = max(x,0) - x target + log1p(exp(-|x|))   BCEWithLogits against a constant label (gan_loss.py:10-31, 34-53, 57-81)
+ *   kind 1: l = max(1 - sgn x, 0), sgn = +1 real / -1 fake   hinge, discriminator side (gan_loss.py:93-98)
+ *   kind 2: l = -x                                           hinge, generator side (gan_loss.py:100-103)
+ *   out[0] = sum_i mask_i l(x_i)      mask: n floats or NULL (= 1)   (gan_loss.py:50-52)
+ * The logit differences are the ones rgan_rate_distortion_trainer.py:37-38, 71-76 and beta_cond_rgan_rate_distortion_trainer.py:43-44,
+ * 78-83 form with `a - b`, and ragan_rate_distortion_trainer.py:35-36, 72-77 with `a - torch.mean(b)`.
+ * fwd: stats (2 floats, written in the centred form only) = {mean(q), sum(q)}: the backward reads the mean from there, so nothing is
+ * read back by the host.  bwd: g = device scalar (upstream gradient); dp_i = g gscale mask_i l'(x_i) with l' = sigmoid(x) - target |
+ * -sgn where 1 - sgn x > 0 else 0 | -1;  paired: dq_i = -dp_i;  centred: dq_j = -(sum_i dp_i) / nq for all j.  dp / dq may be NULL.
+ * All sums: per-block partials, then one block, in an order fixed by (n, nq) -- no atomics, bit-reproducible.
+ * ws: crdr_gan_loss_workspace(n, nq) bytes (nq = 0 without q), the same for both directions.  Pointers must be 4-byte aligned. */
+typedef struct crdr_gan_loss_desc {
+  int64_t n, nq;
+  int32_t kind, center;
+  float target, sgn;
+} crdr_gan_loss_desc;
+size_t crdr_gan_loss_workspace(int64_t n, int64_t nq);
+int crdr_gan_loss_fwd(const crdr_gan_loss_desc* d, const float* p, const float* q, const float* mask, float* out, float* stats,
+                      void* ws, size_t ws_bytes, crdr_stream_t s);
+int crdr_gan_loss_bwd(const crdr_gan_loss_desc* d, const float* p, const float* q, const float* mask, const float* stats,
+                      const float* g, float gscale, float* dp, float* dq, void* ws, size_t ws_bytes, crdr_stream_t s);
 /* out[0] = sum |a-b| ; backward da = sign(a-b) g gscale (sign(0) = 0), db = -da   (distortion_loss.py:49-58, nn.L1Loss) */
 int crdr_l1_sum(const float* a, const float* b, int64_t n, float* out, void* ws, size_t ws_bytes, crdr_stream_t s);
 int crdr_l1_bwd(const float* a, const float* b, int64_t n, const float* g, float gscale, float* da, float* db, crdr_stream_t s);
