@@ -75,6 +75,10 @@ class ChannelNormDesc(C.Structure):
         ("slope", C.c_float), ("eps", C.c_float)]
 
 
+class InstanceNormDesc(C.Structure):  # mirrors struct crdr_instance_norm_desc
+    _fields_ = [("HW", C.c_int64)] + [(n, C.c_int32) for n in ("N", "C", "ldx", "ldy", "act")] + [("slope", C.c_float), ("eps", C.c_float)]
+
+
 class GanLossDesc(C.Structure):  # mirrors struct crdr_gan_loss_desc
     _fields_ = [("n", C.c_int64), ("nq", C.c_int64), ("kind", C.c_int32), ("center", C.c_int32), ("target", C.c_float), ("sgn", C.c_float)]
 
@@ -148,6 +152,9 @@ SIGNATURES = {
     "crdr_channel_norm_workspace": (_SZ, [C.POINTER(ChannelNormDesc)]),
     "crdr_channel_norm_fwd": (_I, [C.POINTER(ChannelNormDesc), _P, _P, _P, _P, _P, _P, _P]),
     "crdr_channel_norm_bwd": (_I, [C.POINTER(ChannelNormDesc), _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _SZ, _P]),
+    "crdr_instance_norm_workspace": (_SZ, [C.POINTER(InstanceNormDesc)]),
+    "crdr_instance_norm_fwd": (_I, [C.POINTER(InstanceNormDesc), _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "crdr_instance_norm_bwd": (_I, [C.POINTER(InstanceNormDesc), _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _SZ, _P]),
     "crdr_reflect_pad_fwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "crdr_reflect_pad_bwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "crdr_pixel_shuffle_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),

@@ -65,7 +65,11 @@ class GANRateDistortionTrainer(RateDistortionTrainer):
         super()._set_optimizer_scheduler()
         oo = deepcopy(self.opt.optim)
         self.d_optimizer = build_optimizer(dict(self.discriminator.named_parameters()), oo.d_optimizer)
-        if hasattr(self.discriminator, "subD_list") and len(self.d_optimizer.param_groups) == 1:
+        if hasattr(self.discriminator, "partition_modules") and len(self.d_optimizer.param_groups) == 1:
+            # a rate-aware discriminator names its own partitions (shared backbone + heads, ...) and, per rate, the ones a step trains
+            # (partitions_for): multirate_clic21_gvae_discriminator.py
+            self.d_optimizer.set_partitions(self.discriminator.partition_modules())
+        elif hasattr(self.discriminator, "subD_list") and len(self.d_optimizer.param_groups) == 1:
             # one partition per sub-discriminator: only the one a step ran is zeroed / all-reduced / updated, like
             # torch.optim.Adam skipping the parameters whose .grad is None (module_list_discriminator.py:26-30)
             self.d_optimizer.set_partitions(self.discriminator.subD_list)

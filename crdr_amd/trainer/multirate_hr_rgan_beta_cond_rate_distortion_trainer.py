@@ -104,7 +104,9 @@ class MultirateBetaCondHrrGanRateDistortionTrainer(BetaConditions, MultirateHigh
                       else self.discriminator(ctx["real"], rate_ind=q))
         else:
             # one pass over [x̂; x] (the discriminator has no batch statistics -- norm_type none -- so this equals the
-            # reference's two separate calls per sample) halves the launches and doubles the rows of every GEMM
+            # reference's two separate calls per sample) halves the launches and doubles the rows of every GEMM.  The rate-aware
+            # discriminators (multirate_clic21_gvae_discriminator.py) keep no chain handle and always come here; their norm_type IN
+            # takes its moments per image, so a sample's output does not depend on what else is in the batch either
             both = self.discriminator(torch.cat([ctx["fake"], ctx["real"]], dim=0), rate_ind=q)
             fake_d, real_d = both[: both.shape[0] // 2], both[both.shape[0] // 2:]
         l_d_real = self.gan_loss.forward_diff(real_d, fake_d.detach(), is_real=True, is_disc=True) * 0.5
@@ -115,8 +117,11 @@ class MultirateBetaCondHrrGanRateDistortionTrainer(BetaConditions, MultirateHigh
                 "out_d_real": real_d.detach().mean(), "out_d_fake": fake_d.detach().mean()}
 
     def _d_parts(self, q):
-        """The optimiser partition of the sub-discriminator that rate level q trains (None = everything)."""
-        return [int(q)] if self.d_optimizer.param_groups[0].get("parts") and len(self.d_optimizer.param_groups[0]["parts"]) > 1 else None
+        """The optimiser partitions that rate level q trains (None = everything): the sub-discriminator's, or what a rate-aware
+        discriminator names itself (partitions_for)."""
+        if not (self.d_optimizer.param_groups[0].get("parts") and len(self.d_optimizer.param_groups[0]["parts"]) > 1):
+            return None
+        return list(self.discriminator.partitions_for(q)) if hasattr(self.discriminator, "partitions_for") else [int(q)]
 
     def _seg_dstep(self, ctx: Dict) -> Dict:
         self.d_optimizer.step(skip=ctx["bad"], partitions=self._d_parts(ctx["q"]))

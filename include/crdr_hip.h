@@ -583,6 +583,36 @@ int crdr_reflect_pad_bwd(const float* dy, int N, int H, int W, int C, int lddy, 
                          crdr_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------ */
+/* InstanceNorm (optional registered op: the reference's rate-aware discriminators with norm_type IN,  */
+/* multirate_clic21_gvae_discriminator.py:12-24,77-119)                                                */
+/* ------------------------------------------------------------------------------------------------ */
+/* multirate_clic21_gvae_discriminator.py:15,22-23 (nn.InstanceNorm2d(out_ch) then nn.LeakyReLU(0.2)): per image n and channel c of an NHWC
+ * tensor [N][HW][C],
+ *   mu = mean_hw x[n][.][c],  var = mean_hw (x[n][.][c] - mu)^2   (BIASED, unlike ChannelNorm's),  rstd = rsqrt(var + eps),
+ *   z = gamma[c] (x - mu) rstd + beta[c],   y = act(z)
+ * without running statistics (train and eval agree).  The variance is taken from centred values: per slab of pixels (mean, M2) around the
+ * slab's own mean, slabs merged in slab order by Chan's formula.  HW >= 2 (torch refuses a single value per channel in training mode too).
+ * C % 4 == 0, 4 <= C <= 1024; strides in floats, multiples of 4, >= C (channel slices of wider NHWC tensors); all tensor pointers 16-byte
+ * aligned; element offsets are 64-bit.  gamma / beta are [C] and may be NULL (affine=False, what the discriminators use). */
+typedef struct crdr_instance_norm_desc {
+  int64_t HW;                      /* pixels per image */
+  int32_t N, C, ldx, ldy;
+  int32_t act;                     /* 0 none, 1 ReLU, 2 LeakyReLU(slope) */
+  float slope, eps;                /* nn.InstanceNorm2d's eps default is 1e-5 */
+} crdr_instance_norm_desc;
+/* bytes of the workspace of either direction (fixed-order slab partials per (n, c), then the backward's two column sums per (n, c)) */
+size_t crdr_instance_norm_workspace(const crdr_instance_norm_desc* d);
+/* stats: 2 N C floats, [n][0][c] = mu, [n][1][c] = rstd, kept for the backward.  Three launches: slab partials, merge, apply. */
+int crdr_instance_norm_fwd(const crdr_instance_norm_desc* d, const float* x, const float* gamma, const float* beta, float* y, float* stats,
+                           void* ws, size_t ws_bytes, crdr_stream_t s);
+/* autograd of the above: xhat and z are recomputed from x and the stats by the forward's own expressions, the activation's derivative is
+ * taken from the recomputed z;  dx = rstd (gh - mean_hw gh - xhat mean_hw(gh xhat)) with gh = gamma dz, dz = act'(z) dy.
+ * dgamma += sum_n sum_hw dz xhat, dbeta += sum_n sum_hw dz (ACCUMULATE; either may be NULL).  No atomics: slab partials, a merge in slab
+ * order, images in order. */
+int crdr_instance_norm_bwd(const crdr_instance_norm_desc* d, const float* x, const float* gamma, const float* beta, const float* stats,
+                           const float* dy, int lddy, float* dx, int lddx, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, crdr_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------ */
 /* sub-pixel up-sampling (the ELIC decoders' `pixel_shuffle: True` form, elic_layers.py:16-20)       */
 /* ------------------------------------------------------------------------------------------------ */
 /* nn.PixelShuffle(2) on NHWC memory (elic_layers.py:16-20): x is [N][H][W] pixels of 4C channels in torch's order
