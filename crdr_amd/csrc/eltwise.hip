@@ -332,6 +332,20 @@ __global__ __launch_bounds__(256) void affine_kernel(const float* x, int ldx, co
   }
 }
 
+// y = a + r, then (scale given) y = y * scale[c] + shift[c]: the end of a residual block whose second activation sits in conv2's epilogue
+// (cheng_resblock.py:61-63), with the InterpChAtt that may follow.  16-byte quads; a or r may alias y
+__global__ __launch_bounds__(256) void add_affine_kernel(const float* a, int lda, const float* r, int ldr, const float* scale, const float* shift,
+                                                         float* y, int ldy, int64_t M, int C4) {
+  const int64_t total = M * C4;
+  for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < total; e += gridDim.x * 256ll) {
+    const int64_t m = e / C4;
+    const int c = (int)(e - m * C4) * 4;
+    f32x4 v = *reinterpret_cast<const f32x4*>(a + m * lda + c) + *reinterpret_cast<const f32x4*>(r + m * ldr + c);
+    if (scale) v = v * *reinterpret_cast<const f32x4*>(scale + c) + *reinterpret_cast<const f32x4*>(shift + c);
+    *reinterpret_cast<f32x4*>(y + m * ldy + c) = v;
+  }
+}
+
 __global__ __launch_bounds__(256) void colsum_kernel(const float* x, int ldx, int64_t M, int C, float* partial,
                                                      int rows_per_block) {
   __shared__ float red[4][64];
@@ -421,6 +435,36 @@ __global__ __launch_bounds__(256) void lrp_bwd_kernel(const float* dy, int lddy,
     const int c = (int)(e - m * C);
     const float t = tanhf(z[m * ldz + c]);
     dz[m * lddz + c] = dy[m * lddy + c] * 0.5f * (1.f - t * t);
+  }
+}
+
+// y = tanh(x) on NHWC rows and dx = dy (1 - y^2) from the saved output (the Cheng20 decoders' output non-linearity,
+// cheng20_autoencoder.py:104-105).  A row is C4 16-byte quads; lanes at index >= C (the image layout's fourth lane) are WRITTEN as zero
+// in both directions, whatever x / dy hold there.  Every element is read and written by the same thread: x may alias y, dy may alias dx.
+__global__ __launch_bounds__(256) void tanh_fwd_kernel(const float* x, int ldx, int64_t M, int C, int C4, float* y, int ldy) {
+  const int64_t total = M * C4;
+  for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < total; e += gridDim.x * 256ll) {
+    const int64_t m = e / C4;
+    const int c = (int)(e - m * C4) * 4;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(x + m * ldx + c);
+    f32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = c + k < C ? tanhf(v[k]) : 0.f;
+    *reinterpret_cast<f32x4*>(y + m * ldy + c) = o;
+  }
+}
+__global__ __launch_bounds__(256) void tanh_bwd_kernel(const float* y, int ldy, const float* dy, int lddy, int64_t M, int C, int C4,
+                                                       float* dx, int lddx) {
+  const int64_t total = M * C4;
+  for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < total; e += gridDim.x * 256ll) {
+    const int64_t m = e / C4;
+    const int c = (int)(e - m * C4) * 4;
+    const f32x4 t = *reinterpret_cast<const f32x4*>(y + m * ldy + c);
+    const f32x4 g = *reinterpret_cast<const f32x4*>(dy + m * lddy + c);
+    f32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = c + k < C ? g[k] * (1.f - t[k] * t[k]) : 0.f;
+    *reinterpret_cast<f32x4*>(dx + m * lddx + c) = o;
   }
 }
 
@@ -1110,6 +1154,19 @@ extern "C" int crdr_affine(const float* x, int ldx, const float* scale, const fl
   return 0;
 }
 
+extern "C" int crdr_add_affine(const float* a, int lda, const float* r, int ldr, const float* scale, const float* shift, float* y, int ldy,
+                               int64_t M, int C, crdr_stream_t s) {
+  CRDR_REQUIRE(a && r && y && (!scale == !shift), "add_affine: null pointer (scale and shift come together)");
+  CRDR_REQUIRE(M >= 0 && C > 0 && C % 4 == 0 && lda % 4 == 0 && ldr % 4 == 0 && ldy % 4 == 0 && lda >= C && ldr >= C && ldy >= C,
+               "add_affine: C (%d) and the strides (%d, %d, %d) must be multiples of 4, the strides at least C", C, lda, ldr, ldy);
+  CRDR_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(y) |
+                 reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 15) == 0, "add_affine: operands must be 16-byte aligned");
+  if (M == 0) return 0;
+  hipLaunchKernelGGL(add_affine_kernel, dim3(grid_for(M * (C / 4))), dim3(256), 0, as_stream(s), a, lda, r, ldr, scale, shift, y, ldy, M, C / 4);
+  CRDR_CHECK_LAUNCH("add_affine");
+  return 0;
+}
+
 extern "C" size_t crdr_colsum_workspace(int64_t M, int C) {
   int rpb;
   return (size_t)ebwd_blocks(M, &rpb) * C * sizeof(float);
@@ -1195,6 +1252,33 @@ extern "C" int crdr_lrp_bwd(const float* dy, int lddy, const float* z, int ldz, 
   if (M * C == 0) return 0;
   hipLaunchKernelGGL(lrp_bwd_kernel, dim3(grid_for(M * C)), dim3(256), 0, as_stream(s), dy, lddy, z, ldz, dz, lddz, M, C);
   CRDR_CHECK_LAUNCH("lrp_bwd");
+  return 0;
+}
+
+// what both tanh entry points ask of an operand: a 16-byte aligned pointer and a stride that is a multiple of 4 and holds the row's quads
+static bool tanh_operand_ok(const float* p, int ld, int C) {
+  return p && (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 4 == 0 && ld >= round_up(C, 4);
+}
+extern "C" int crdr_tanh_fwd(const float* x, int ldx, int64_t M, int C, float* y, int ldy, crdr_stream_t s) {
+  CRDR_REQUIRE(M >= 0 && C > 0, "tanh_fwd: M (%lld) and C (%d) out of range", (long long)M, C);
+  CRDR_REQUIRE(tanh_operand_ok(x, ldx, C) && tanh_operand_ok(y, ldy, C),
+               "tanh_fwd: operands are 16-byte aligned, their strides multiples of 4 and at least C rounded up to 4");
+  CRDR_REQUIRE(x != y || ldx == ldy, "tanh_fwd: in place needs one stride");
+  if (M == 0) return 0;
+  const int C4 = round_up(C, 4) / 4;
+  hipLaunchKernelGGL(tanh_fwd_kernel, dim3(grid_for(M * C4)), dim3(256), 0, as_stream(s), x, ldx, M, C, C4, y, ldy);
+  CRDR_CHECK_LAUNCH("tanh_fwd");
+  return 0;
+}
+extern "C" int crdr_tanh_bwd(const float* y, int ldy, const float* dy, int lddy, int64_t M, int C, float* dx, int lddx, crdr_stream_t s) {
+  CRDR_REQUIRE(M >= 0 && C > 0, "tanh_bwd: M (%lld) and C (%d) out of range", (long long)M, C);
+  CRDR_REQUIRE(tanh_operand_ok(y, ldy, C) && tanh_operand_ok(dy, lddy, C) && tanh_operand_ok(dx, lddx, C),
+               "tanh_bwd: operands are 16-byte aligned, their strides multiples of 4 and at least C rounded up to 4");
+  CRDR_REQUIRE(dy != dx || lddy == lddx, "tanh_bwd: in place needs one stride");
+  if (M == 0) return 0;
+  const int C4 = round_up(C, 4) / 4;
+  hipLaunchKernelGGL(tanh_bwd_kernel, dim3(grid_for(M * C4)), dim3(256), 0, as_stream(s), y, ldy, dy, lddy, M, C, C4, dx, lddx);
+  CRDR_CHECK_LAUNCH("tanh_bwd");
   return 0;
 }
 

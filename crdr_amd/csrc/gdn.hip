@@ -52,8 +52,9 @@ __global__ __launch_bounds__(256) void gdn_square_kernel(const float* x, int ldx
   }
 }
 
+// y = x n^(-1/2) or x n^(1/2), plus the shortcut where `res` is given (crdr_gdn_res_fwd beyond 192 channels)
 __global__ __launch_bounds__(256) void gdn_apply_kernel(const float* x, int ldx, const float* norm, int64_t M, int C4, int inverse,
-                                                        float* y, int ldy) {
+                                                        const float* res, int ldres, float* y, int ldy) {
   const int64_t total = M * C4;
   for (int64_t e = blockIdx.x * 256ll + threadIdx.x; e < total; e += gridDim.x * 256ll) {
     const int64_t m = e / C4;
@@ -63,6 +64,7 @@ __global__ __launch_bounds__(256) void gdn_apply_kernel(const float* x, int ldx,
     f32x4 o;
 #pragma unroll
     for (int k = 0; k < 4; ++k) o[k] = inverse ? v[k] * sqrtf(n[k]) : v[k] / sqrtf(n[k]);
+    if (res) o += *reinterpret_cast<const f32x4*>(res + m * ldres + c);
     *reinterpret_cast<f32x4*>(y + m * ldy + c) = o;
   }
 }
@@ -148,6 +150,14 @@ struct GdnFusedArgs {
   unsigned x_bytes, pack_bytes;
 };
 
+// the shortcut of crdr_gdn_res_fwd rides behind the plain arguments: the kernels without it keep the argument block they had
+struct GdnFusedResArgs : GdnFusedArgs {
+  const float* res;   // [M][ldres], added to y
+  int ldres;
+};
+template <bool RES>
+using GdnFusedArgsFor = std::conditional_t<RES, GdnFusedResArgs, GdnFusedArgs>;
+
 constexpr int kGdnBM = 64;
 
 // x^2 of a fragment on the way to the matrix cores: two v_pk_mul_f32.  Nothing vector hides beside an exact-fp32 MFMA and a packed
@@ -163,8 +173,23 @@ __device__ __forceinline__ void gdn_wait_barrier() {   // vmcnt(VM) lgkmcnt(0), 
   __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int NS, int OP>   // OP 0: y = x n^(-1/2) (GDN); 1: y = x n^(1/2) (IGDN); 2: y = n
-__global__ __launch_bounds__(256) void gdn_fused_fwd_kernel(const GdnFusedArgs p) {
+// RES (crdr_gdn_res_fwd: cheng_resblock.py:61-63, 104-107): y += res.  A lane loads the shortcut at exactly the positions of its stores -- the
+// (rb, cb) offsets of store_piece on the pixel stride ldres, through a descriptor of the tile's valid rows -- so the range check drops the
+// ragged last tile's missing rows and the padded channels as it does for the stores, nothing crosses waves, and there is no new barrier and
+// no new LDS.  The NS loads (one per (rb, cb), 16 bytes per lane) go out in the SECOND half of the matrix loop's groups, load q directly
+// behind store q of the previous tile and INTO the registers that store gives up (yout), so the kernel holds no more than it
+// did (issued in the first half, beside the LDS-DMA requests, the NS x 4 extra registers stay live across the loop).
+// Request counting with RES: a tile issues, in order, the NS DMA requests of the next tile and then NS x (store of the previous tile,
+// shortcut load).  Requests return to the wave in order, and the epilogue consumes every shortcut register, the youngest request of the
+// tile included, behind the compiler's own vmcnt wait: after the epilogue NOTHING of the tile is in flight.  "All but the NS youngest" at
+// the next barrier would name a mix of stores and loads, so the RES kernels say what holds instead, gdn_wait_barrier<0>: it costs nothing
+// (the count is already zero) and the hand-over of the x buffer does not rest on a wait the compiler chose.  What RES pays is the exposed
+// tail of the last shortcut loads and of the previous tile's stores in the epilogue, once per tile.
+// Without RES nothing changed: NS DMA requests, then NS stores, gdn_wait_barrier<NS>; those instantiations are the code they were before
+// the parameter existed (equal register, LDS and scratch figures: DESIGN 15).
+template <int NS, int OP, bool RES = false>   // OP 0: y = x n^(-1/2) (GDN); 1: y = x n^(1/2) (IGDN); 2: y = n
+__global__ __launch_bounds__(256) void gdn_fused_fwd_kernel(const GdnFusedArgsFor<RES> p) {
+  static_assert(!(RES && OP == 2), "the norm has no shortcut");
   constexpr int BM = kGdnBM, NCB = NS / 4, NBX = NS / 2, XF = NBX * BM * 32;   // NBX chunk images of 32 channels; XF floats per x tile
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* sX = smem;                    // [2][NBX][BM * 32]
@@ -212,6 +237,8 @@ __global__ __launch_bounds__(256) void gdn_fused_fwd_kernel(const GdnFusedArgs p
     xe[cb] = (ch >> 5) * BM * 32 + lds_off(ln, (ch & 31) >> 2);
   }
   const unsigned ybase = ((unsigned)ln * p.ldy + col0 + 4 * lg) * 4u;
+  unsigned rbase = 0;   // the shortcut's counterpart of ybase
+  if constexpr (RES) rbase = ((unsigned)ln * p.ldres + col0 + 4 * lg) * 4u;
   auto tile_rsrc = [&](const float* base, int ld, long long m0) __attribute__((always_inline)) {
     const long long left = p.M - m0;
     const long long bytes = left <= 0 ? 0 : ((left < BM ? left : BM) - 1) * ld * 4ll + p.C * 4ll;   // (a tile past the last one: no bytes at all)
@@ -249,7 +276,7 @@ __global__ __launch_bounds__(256) void gdn_fused_fwd_kernel(const GdnFusedArgs p
     // this tile's x has landed (everything but the NS result stores issued after its requests, the youngest ones); every wave is done with the other
     // buffer (matrix loop AND epilogue: the results leave from registers, nothing is rewritten in LDS -- this is the only barrier of a tile)
     if (first) gdn_wait_barrier<0>();
-    else gdn_wait_barrier<NS>();
+    else gdn_wait_barrier<RES ? 0 : NS>();
     first = false;
     // the next tile's NS requests go out one per group of the matrix loop, behind that group's MFMAs (an LDS-DMA request issued among bare
     // MFMAs costs ~60 cycles of issue; twelve in a row at the top of the tile were 22 us of the launch).  No branch: past the last tile the
@@ -261,6 +288,28 @@ __global__ __launch_bounds__(256) void gdn_fused_fwd_kernel(const GdnFusedArgs p
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
     float* xt = sX + cur * XF;
+    // this tile's shortcut: request q is (rb, cb) = (q / NCB, q % NCB), the positions of store_piece(q), and lands in the registers that
+    // store has just given up -- yout[rb][cb] holds the shortcut from here to the epilogue, which adds the result to it
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t rr = ry_prev;
+    __amdgpu_buffer_rsrc_t ry = ry_prev;   // this tile's results (without RES: made in front of the epilogue, where it always was)
+    if constexpr (RES) {
+      rr = tile_rsrc(p.res, p.ldres, m0);
+      // the descriptor's branches would otherwise sit between the matrix loop and the epilogue and make the epilogue a basic block of its
+      // own: every accumulator is then copied out at its top (NS x 4 registers: harmless where the result registers are free, but here
+      // they hold the shortcut -- 24 loop invariants went to the accumulator file and came back once per tile)
+      ry = tile_rsrc(p.y, p.ldy, m0);
+      // the NS load offsets are rebuilt from the lane's base in every tile (the base is made opaque here, as in the backward kernel):
+      // hoisted out of the tile loop as NS more invariants they do not all fit the 256 architectural registers at 192 channels (4 of them
+      // were parked in the accumulator file)
+      asm volatile("" : "+v"(rbase));
+    }
+    auto res_piece = [&](int q) __attribute__((always_inline)) {
+      if constexpr (RES) {
+        const int rb = q / NCB, cb = q % NCB;
+        yout[rb][cb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+            rr, chok[cb] ? rbase + (unsigned)(16 * rb * p.ldres * 4 + 64 * cb) : 0x80000000u, 0, 0));
+      }
+    };
     // 2 NS groups (K step s, row blocks rb, rb + 1) of 8 NCB MFMAs on 2 NCB independent accumulators (with one row block per group -- three
     // accumulators in turn -- the loop ran at 44 cycles per MFMA, with two at 40; the instruction's issue rate is 32, its dependent latency
     // 40).  The pixel fragments of group g + 1 (pixel rows 16 rb + ln, channels 16 s + 4 lg .. + 3: chunk image s >> 1, slot 4 (s & 1) + lg) are
@@ -284,13 +333,13 @@ __global__ __launch_bounds__(256) void gdn_fused_fwd_kernel(const GdnFusedArgs p
           acc[rb + 1][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(B[cb][s][e], a1[e], acc[rb + 1][cb], 0, 0, 0);
         }
       if (g < NS) fetch_piece(rnext, cur ^ 1, g);
-      else store_piece(ry_prev, g - NS);
+      else { store_piece(ry_prev, g - NS); res_piece(g - NS); }
       __builtin_amdgcn_sched_barrier(0);
     }
     // epilogue: acc[rb][cb][i] is (pixel row 16 rb + ln, channel ch(cb) + i); x comes from the LDS tile again, the result leaves with one
     // 16-byte store per (rb, cb) -- 64-byte row segments, the two halves of a 128-byte line in consecutive instructions of the wave.
     // (v_rsq_f32 / v_sqrt_f32: 1 ulp, one instruction each; n >= beta_min > 0: no denormal path)
-    const __amdgpu_buffer_rsrc_t ry = tile_rsrc(p.y, p.ldy, m0);
+    if constexpr (!RES) ry = tile_rsrc(p.y, p.ldy, m0);
 #pragma unroll
     for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
@@ -303,6 +352,7 @@ __global__ __launch_bounds__(256) void gdn_fused_fwd_kernel(const GdnFusedArgs p
           const float n = acc[rb][cb][i] + bta[i];
           y[i] = OP == 2 ? n : (OP == 1 ? xv[i] * __builtin_amdgcn_sqrtf(n) : xv[i] * __builtin_amdgcn_rsqf(n));
         }
+        if constexpr (RES) y += yout[rb][cb];
         yout[rb][cb] = y;
       }
     ry_prev = ry;
@@ -311,19 +361,23 @@ __global__ __launch_bounds__(256) void gdn_fused_fwd_kernel(const GdnFusedArgs p
   for (int q = 0; q < NS; ++q) store_piece(ry_prev, q);   // the last tile's results
 }
 
-template <int NS, int OP>
-static void gdn_fused_launch_op(const GdnFusedArgs& a, hipStream_t s) {
+template <int NS, int OP, bool RES>
+static void gdn_fused_launch_op(const GdnFusedArgsFor<RES>& a, hipStream_t s) {
   const size_t lds = ((size_t)2 * (NS / 2) * kGdnBM * 32 + 64 * (NS / 4)) * sizeof(float);
   static std::atomic<bool> done{false};
-  allow_full_lds(done, gdn_fused_fwd_kernel<NS, OP>);
-  hipLaunchKernelGGL((gdn_fused_fwd_kernel<NS, OP>), dim3(std::min(a.tiles, 256)), dim3(256), lds, s, a);
+  allow_full_lds(done, gdn_fused_fwd_kernel<NS, OP, RES>);
+  hipLaunchKernelGGL((gdn_fused_fwd_kernel<NS, OP, RES>), dim3(std::min(a.tiles, 256)), dim3(256), lds, s, a);
 }
 
 template <int NS>
-static void gdn_fused_launch(const GdnFusedArgs& a, hipStream_t s) {
-  if (a.mode) gdn_fused_launch_op<NS, 2>(a, s);
-  else if (a.inverse) gdn_fused_launch_op<NS, 1>(a, s);
-  else gdn_fused_launch_op<NS, 0>(a, s);
+static void gdn_fused_launch(const GdnFusedResArgs& a, hipStream_t s) {
+  if (a.res) {   // (mode 0 only: gdn_fused)
+    if (a.inverse) gdn_fused_launch_op<NS, 1, true>(a, s);
+    else gdn_fused_launch_op<NS, 0, true>(a, s);
+  }
+  else if (a.mode) gdn_fused_launch_op<NS, 2, false>(a, s);
+  else if (a.inverse) gdn_fused_launch_op<NS, 1, false>(a, s);
+  else gdn_fused_launch_op<NS, 0, false>(a, s);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -888,9 +942,11 @@ static int gdn_square(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, cons
   return 0;
 }
 
-// y (mode 0) or n (mode 1) by the fused kernel; gamma_eff / beta_eff must already be in the workspace
-static int gdn_fused(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, const float* x, float* out, int ldo, int mode, crdr_stream_t s) {
-  GdnFusedArgs a;
+// y (mode 0; plus the shortcut where `res` is given) or n (mode 1) by the fused kernel; gamma_eff / beta_eff must already be in the workspace
+static int gdn_fused(const crdr_gdn_desc* d, const GdnLayout& L, char* ws, const float* x, float* out, int ldo, int mode, crdr_stream_t s,
+                     const float* res = nullptr, int ldres = 0) {
+  GdnFusedResArgs a;
+  a.res = mode ? nullptr : res; a.ldres = ldres;
   a.x = x; a.pack = (const float*)(ws + L.pack_f); a.beta = (const float*)(ws + L.beta_eff); a.y = out;
   a.M = d->M; a.C = d->C; a.ldx = d->ldx; a.ldy = ldo; a.inverse = d->inverse; a.mode = mode;
   a.tiles = (int)((d->M + kGdnBM - 1) / kGdnBM);
@@ -1014,22 +1070,43 @@ extern "C" size_t crdr_gdn_workspace(const crdr_gdn_desc* d, int backward) {
   return L.end;
 }
 
+// both forward entry points behind their checks: y = GDN / IGDN(x), plus res where it is given
+static int gdn_forward(const crdr_gdn_desc* d, const GdnLayout& L, const float* x, const float* beta, const float* gamma, const float* res,
+                       int ldres, float* y, char* w8, crdr_stream_t s) {
+  if (gdn_fused_ok(d, L) && (!res || gdn_rows_span(ldres))) {   // reparametrisation + ONE pass over x
+    if (int rc = gdn_reparam(d, L, w8, beta, gamma, s)) return rc;
+    return gdn_fused(d, L, w8, x, y, d->ldy, 0, s, res, ldres);
+  }
+  if (int rc = gdn_norm(d, L, w8, x, beta, gamma, s)) return rc;
+  hipLaunchKernelGGL(gdn_apply_kernel, dim3(grid1(d->M * (d->C / 4))), dim3(256), 0, as_stream(s), x, d->ldx, (const float*)(w8 + L.norm),
+                     d->M, d->C / 4, d->inverse, res, ldres, y, d->ldy);
+  CRDR_CHECK_LAUNCH("gdn_apply");
+  return 0;
+}
+
 extern "C" int crdr_gdn_fwd(const crdr_gdn_desc* d, const float* x, const float* beta, const float* gamma, float* y, void* ws,
                             size_t ws_bytes, crdr_stream_t s) {
   CRDR_REQUIRE(d && x && beta && gamma && y && ws, "gdn_fwd: null pointer");
   GdnLayout L;
   if (int rc = gdn_bind(d, 0, ws, ws_bytes, &L)) return rc;
   CRDR_REQUIRE(d->ldy % 4 == 0 && d->ldy >= d->C, "gdn_fwd: ldy");
-  char* w8 = (char*)ws;
-  if (gdn_fused_ok(d, L)) {   // reparametrisation + ONE pass over x
-    if (int rc = gdn_reparam(d, L, w8, beta, gamma, s)) return rc;
-    return gdn_fused(d, L, w8, x, y, d->ldy, 0, s);
-  }
-  if (int rc = gdn_norm(d, L, w8, x, beta, gamma, s)) return rc;
-  hipLaunchKernelGGL(gdn_apply_kernel, dim3(grid1(d->M * (d->C / 4))), dim3(256), 0, as_stream(s), x, d->ldx, (const float*)(w8 + L.norm),
-                     d->M, d->C / 4, d->inverse, y, d->ldy);
-  CRDR_CHECK_LAUNCH("gdn_apply");
-  return 0;
+  return gdn_forward(d, L, x, beta, gamma, nullptr, 0, y, (char*)ws, s);
+}
+
+extern "C" int crdr_gdn_res_fwd(const crdr_gdn_desc* d, const float* x, const float* beta, const float* gamma, const float* res, int ldres,
+                                float* y, void* ws, size_t ws_bytes, crdr_stream_t s) {
+  CRDR_REQUIRE(d && x && beta && gamma && res && y && ws, "gdn_res_fwd: null pointer");
+  GdnLayout L;
+  if (int rc = gdn_bind(d, 0, ws, ws_bytes, &L)) return rc;
+  CRDR_REQUIRE(d->ldy % 4 == 0 && d->ldy >= d->C, "gdn_res_fwd: ldy");
+  CRDR_REQUIRE(ldres % 4 == 0 && ldres >= d->C, "gdn_res_fwd: ldres (%d) must be a multiple of 4 and at least C (%d)", ldres, d->C);
+  CRDR_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(y)) & 15) == 0,
+               "gdn_res_fwd: x, res and y must be 16-byte aligned");
+  // the byte ranges of the two operands (first to last element) must be disjoint: the kernel reads res while results of other tiles leave
+  const char *r0 = (const char*)res, *r1 = r0 + ((size_t)(d->M - 1) * ldres + d->C) * 4, *y0 = (const char*)y,
+             *y1 = y0 + ((size_t)(d->M - 1) * d->ldy + d->C) * 4;
+  CRDR_REQUIRE(d->M <= 0 || r1 <= y0 || y1 <= r0, "gdn_res_fwd: res overlaps y");
+  return gdn_forward(d, L, x, beta, gamma, res, ldres, y, (char*)ws, s);
 }
 
 extern "C" int crdr_gdn_bwd(const crdr_gdn_desc* d, const float* x, const float* beta, const float* gamma, const float* dy, int lddy,

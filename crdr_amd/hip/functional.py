@@ -379,6 +379,39 @@ def affine(x, scale, shift):
     return _Affine.apply(x, scale, shift)
 
 
+class _AddAffine(torch.autograd.Function):
+    """(a, r, scale?, shift?) -> (a + r) [* scale + shift] in one launch (crdr_add_affine).  Both addends get dy (* scale); the affine's own
+    gradients come from crdr_epilogue_bwd on the saved output, as in _Affine."""
+
+    @staticmethod
+    def forward(ctx, a, r, scale, shift):
+        lib = L.load()
+        a, lda = ops.nhwc(a)
+        r, ldr = ops.nhwc(r)
+        if a.shape != r.shape:
+            raise L.CrdrHipError(f"add_affine: operands of shapes {tuple(a.shape)} and {tuple(r.shape)}")
+        n, c, h, w = a.shape
+        y = ops.empty_nhwc(n, c, h, w, a.device)
+        L.check(lib.crdr_add_affine(a.data_ptr(), lda, r.data_ptr(), ldr, ops._p(scale), ops._p(shift), y.data_ptr(), ops.ld_for(c), n * h * w, c,
+                                    ops._stream()), "add_affine")
+        ctx.save_for_backward(*((y, scale, shift) if scale is not None else ()))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.saved_tensors:
+            return dy, dy, None, None
+        y, scale, shift = ctx.saved_tensors
+        dz, _, _, cs = ops.epilogue_bwd(dy, y, L.EPI_AFFINE, scale=scale, shift=shift)
+        return dz, dz, cs[2], cs[3]
+
+
+def add_affine(a, r, affine: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """a + r, then the (scale, shift) of an InterpChAtt where one follows"""
+    scale, shift = affine if affine is not None else (None, None)
+    return _AddAffine.apply(a, r, scale, shift)
+
+
 class _PixelShuffle(torch.autograd.Function):
     """nn.PixelShuffle(2) on NHWC memory: [N, 4C, H, W] -> [N, C, 2H, 2W] (crdr_pixel_shuffle_fwd / _bwd).  Nothing is saved: the
     backward is the inverse permutation of the cotangent, one launch."""
@@ -439,6 +472,37 @@ class _Lrp(torch.autograd.Function):
 def lrp(a, z):
     """a + 0.5 * tanh(z)"""
     return _Lrp.apply(a, z)
+
+
+class _Tanh(torch.autograd.Function):
+    """torch.tanh on NHWC memory (crdr_tanh_fwd / _bwd); the output is saved, the backward is dy (1 - y^2).  A 3-channel tensor keeps the
+    image layout: pixel stride 4, fourth lane written as zero in both directions."""
+
+    @staticmethod
+    def forward(ctx, x):
+        lib = L.load()
+        x, ldx = ops.nhwc(x)
+        n, c, h, w = x.shape
+        y = ops.empty_nhwc(n, c, h, w, x.device)
+        L.check(lib.crdr_tanh_fwd(x.data_ptr(), ldx, n * h * w, c, y.data_ptr(), ops.ld_for(c), ops._stream()), "tanh_fwd")
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        lib = L.load()
+        dy, lddy = ops.nhwc(dy)
+        n, c, h, w = y.shape
+        dx = ops.empty_nhwc(n, c, h, w, y.device)
+        L.check(lib.crdr_tanh_bwd(y.data_ptr(), ops.ld_for(c), dy.data_ptr(), lddy, n * h * w, c, dx.data_ptr(), ops.ld_for(c),
+                                  ops._stream()), "tanh_bwd")
+        return dx
+
+
+def tanh(x):
+    """torch.tanh(x) for NHWC tensors (the Cheng20 decoders' output non-linearity)"""
+    return _Tanh.apply(x)
 
 
 def gauss_cond_fwd2(d, io, device) -> None:

@@ -149,6 +149,7 @@ SIGNATURES = {
     "crdr_gdn_workspace": (_SZ, [C.POINTER(GdnDesc), _I]),
     "crdr_gdn_fwd": (_I, [C.POINTER(GdnDesc), _P, _P, _P, _P, _P, _SZ, _P]),
     "crdr_gdn_bwd": (_I, [C.POINTER(GdnDesc), _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _SZ, _P]),
+    "crdr_gdn_res_fwd": (_I, [C.POINTER(GdnDesc), _P, _P, _P, _P, _I, _P, _P, _SZ, _P]),
     "crdr_channel_norm_workspace": (_SZ, [C.POINTER(ChannelNormDesc)]),
     "crdr_channel_norm_fwd": (_I, [C.POINTER(ChannelNormDesc), _P, _P, _P, _P, _P, _P, _P]),
     "crdr_channel_norm_bwd": (_I, [C.POINTER(ChannelNormDesc), _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _SZ, _P]),
@@ -186,6 +187,9 @@ SIGNATURES = {
     "crdr_bias_relu_slots": (_I, [_P, _I, _I64, _I, _I, _P, _P, _P]),
     "crdr_lrp": (_I, [_P, _I, _P, _I, _P, _I, _I64, _I, _P]),
     "crdr_lrp_bwd": (_I, [_P, _I, _P, _I, _P, _I, _I64, _I, _P]),
+    "crdr_add_affine": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I64, _I, _P]),
+    "crdr_tanh_fwd": (_I, [_P, _I, _I64, _I, _P, _I, _P]),
+    "crdr_tanh_bwd": (_I, [_P, _I, _P, _I, _I64, _I, _P, _I, _P]),
     "crdr_gauss_cond_fwd": (_I, [C.POINTER(GcDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "crdr_gauss_cond_bwd": (_I, [C.POINTER(GcDesc), _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "crdr_entropy_bottleneck_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P]),

@@ -408,6 +408,14 @@ int crdr_linear_group_bwd(const float* x, int M, int I, int ldx, const crdr_line
 /* y[m][c] = x[m][c] * scale[c] + shift[c]   (stand-alone InterpChAtt apply) */
 int crdr_affine(const float* x, int ldx, const float* scale, const float* shift, float* y, int ldy, int64_t M, int C,
                 crdr_stream_t s);
+/* y = a + r, then with scale / shift (both or neither) y = y * scale[c] + shift[c]: the sum that ends a residual block whose second
+ * activation is conv2's epilogue (cheng_resblock.py:61-63 `x = self.actv2(x); x = x + shortcut`) and the InterpChAtt that may follow it
+ * (cheng20_interpca_autoencoder.py:39-40).  The conv epilogue has LRELU, RES and AFFINE in this order, but crdr_epilogue_bwd refuses an
+ * activation with RES / AFFINE behind it (the mask cannot be recovered from the saved output), so training keeps the sum apart.  C and
+ * the strides are multiples of 4, pointers 16-byte aligned (scale / shift too); a or r may be y.  Backward: da = dr = dy (* scale), the
+ * AFFINE case through crdr_epilogue_bwd on the saved y. */
+int crdr_add_affine(const float* a, int lda, const float* r, int ldr, const float* scale, const float* shift, float* y, int ldy, int64_t M,
+                    int C, crdr_stream_t s);
 /* out[c] (+)= sum_m x[m][c] */
 size_t crdr_colsum_workspace(int64_t M, int C);
 int crdr_colsum(const float* x, int ldx, int64_t M, int C, float* out, int accumulate, void* ws, size_t ws_bytes,
@@ -436,6 +444,14 @@ int crdr_bias_relu_slots(float* a, int ld, int64_t M, int C, int n, const int32_
 int crdr_lrp(const float* a, int lda, const float* z, int ldz, float* y, int ldy, int64_t M, int C, crdr_stream_t s);
 int crdr_lrp_bwd(const float* dy, int lddy, const float* z, int ldz, float* dz, int lddz, int64_t M, int C,
                  crdr_stream_t s);
+
+/* y = tanh(x) on M NHWC rows of C channels (the Cheng20 decoders' `if self.use_tanh: x = torch.tanh(x)`, cheng20_autoencoder.py:104-105,
+ * cheng20_interpca_autoencoder.py:72-73) and its backward from the saved output, dx = dy (1 - y^2).  Rows move in 16-byte quads: C is
+ * rounded up to a multiple of 4 inside the strides and the lanes at index >= C are WRITTEN AS ZERO in both directions (C == 3: the image
+ * layout keeps its zero fourth lane, as crdr_pixel_shuffle_fwd leaves it).  Strides are in floats, multiples of 4 and at least the rounded
+ * row width; pointers 16-byte aligned; x may be y and dy may be dx (with one stride); anything else is refused. */
+int crdr_tanh_fwd(const float* x, int ldx, int64_t M, int C, float* y, int ldy, crdr_stream_t s);
+int crdr_tanh_bwd(const float* y, int ldy, const float* dy, int lddy, int64_t M, int C, float* dx, int lddx, crdr_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------ */
 /* entropy models (CompressAI 1.2.4 semantics as called from the reference)                          */
@@ -545,6 +561,14 @@ int crdr_gdn_fwd(const crdr_gdn_desc* d, const float* x, const float* beta, cons
                  crdr_stream_t s);
 int crdr_gdn_bwd(const crdr_gdn_desc* d, const float* x, const float* beta, const float* gamma, const float* dy, int lddy, float* dx,
                  int lddx, float* dbeta, float* dgamma, void* ws, size_t ws_bytes, crdr_stream_t s);
+/* GDN / IGDN with the block's shortcut added in the same pass (cheng_resblock.py:61-63 `x = self.actv2(x); x = x + shortcut`, :104-107
+ * `return x + shortcut` behind the IGDN that ends c1):  y[p][c] = GDN_or_IGDN(x)[p][c] + res[p][c].  One launch moves 12 B per element
+ * where crdr_gdn_fwd and a separate add move 20.  Every channel count crdr_gdn_fwd serves; workspace crdr_gdn_workspace(d, 0).  res is
+ * [M] rows of pixel stride ldres (a multiple of 4, >= C: a channel slice of a wider NHWC tensor is fine); x, res and y are 16-byte aligned
+ * and the byte ranges of res and y are disjoint; anything else is refused.  There is no backward of its own: the shortcut's gradient is
+ * dy itself and the GDN's is crdr_gdn_bwd on the same dy. */
+int crdr_gdn_res_fwd(const crdr_gdn_desc* d, const float* x, const float* beta, const float* gamma, const float* res, int ldres, float* y,
+                     void* ws, size_t ws_bytes, crdr_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------ */
 /* ChannelNorm and reflection padding (optional registered ops: the reference's HiFiC transforms,      */
