@@ -444,6 +444,54 @@ def pixel_shuffle(x):
     return _PixelShuffle.apply(x)
 
 
+UPSAMPLE16_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}   # crdr_upsample16_desc.mode
+
+
+class _Upsample16Cat(torch.autograd.Function):
+    """(img [N,3,16h,16w], cond [N,Cc,h,w]) -> torch.cat((img, F.interpolate(cond, scale_factor=16, mode)), dim=1) in dense NHWC memory of
+    pixel stride Cc + 4, pad lane zero (crdr_upsample16_cat_fwd / _bwd).  Nothing is saved: the backward is linear in the cotangent.  An
+    input that needs no gradient gets a null pointer, and the kernels skip its share of the work."""
+
+    @staticmethod
+    def forward(ctx, img, cond, mode: int):
+        lib = L.load()
+        img, ldi = ops.nhwc(img)
+        cond, ldc = ops.nhwc(cond)
+        n, cc, h, w = cond.shape
+        if tuple(img.shape) != (n, 3, 16 * h, 16 * w):
+            raise L.CrdrHipError(f"upsample16_cat: image of shape {tuple(img.shape)} for a condition of shape {tuple(cond.shape)}")
+        ldo = ops.ld_for(3 + cc)
+        buf = torch.empty((n, 16 * h, 16 * w, ldo), dtype=torch.float32, device=img.device)   # every lane is written, the pad lanes as zeros
+        d = L.Upsample16Desc(N=n, h=h, w=w, Cc=cc, ldi=ldi, ldc=ldc, ldo=ldo, mode=mode)
+        L.check(lib.crdr_upsample16_cat_fwd(C.byref(d), img.data_ptr(), cond.data_ptr(), buf.data_ptr(), ops._stream()), "upsample16_cat_fwd")
+        ctx.geom = (n, cc, h, w, mode)
+        return buf.permute(0, 3, 1, 2)[:, :3 + cc]
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = L.load()
+        n, cc, h, w, mode = ctx.geom
+        dout, ldo = ops.nhwc(dout)
+        dev = dout.device
+        dimg = torch.empty((n, 16 * h, 16 * w, 4), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        dcond = torch.empty((n, h, w, cc), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        d = L.Upsample16Desc(N=n, h=h, w=w, Cc=cc, ldi=4, ldc=cc, ldo=ldo, mode=mode)
+        ws, wsn = ops.workspace(lib.crdr_upsample16_cat_workspace(C.byref(d)), dev) if dcond is not None else (None, 0)
+        L.check(lib.crdr_upsample16_cat_bwd(C.byref(d), dout.data_ptr(), ops._p(dimg), ops._p(dcond), ws, wsn, ops._stream()), "upsample16_cat_bwd")
+        return (None if dimg is None else dimg.permute(0, 3, 1, 2)[:, :3], None if dcond is None else dcond.permute(0, 3, 1, 2), None)
+
+
+def upsample16_cat(img, cond, mode="bilinear"):
+    """torch.cat((img, F.interpolate(cond, scale_factor=16, mode=mode, align_corners=False)), dim=1) for a 3-channel image and a condition
+    of Cc % 4 == 0 channels: the NCHW view [:, :3 + Cc] of a dense NHWC buffer, the form HipConv2d takes a channel count that is no
+    multiple of 4 in.  `mode` is 'nearest', 'bilinear' or 'bicubic' (or the descriptor's number)."""
+    if isinstance(mode, str):
+        if mode not in UPSAMPLE16_MODES:
+            raise L.CrdrHipError(f"upsample16_cat: mode {mode!r} (one of {sorted(UPSAMPLE16_MODES)})")
+        mode = UPSAMPLE16_MODES[mode]
+    return _Upsample16Cat.apply(img, cond, int(mode))
+
+
 class _Lrp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, z):

@@ -83,6 +83,10 @@ class GanLossDesc(C.Structure):  # mirrors struct crdr_gan_loss_desc
     _fields_ = [("n", C.c_int64), ("nq", C.c_int64), ("kind", C.c_int32), ("center", C.c_int32), ("target", C.c_float), ("sgn", C.c_float)]
 
 
+class Upsample16Desc(C.Structure):  # mirrors struct crdr_upsample16_desc
+    _fields_ = [(n, C.c_int32) for n in ("N", "h", "w", "Cc", "ldi", "ldc", "ldo", "mode")]
+
+
 class GcDesc2(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("N", "HW", "C", "ldy", "ldmu", "ldsigma", "ldyhat", "ldyhat2", "ldnoise", "ldlik",
                                          "ldgrad", "lddyhat", "Ctot", "c0")] + [
@@ -160,6 +164,9 @@ SIGNATURES = {
     "crdr_reflect_pad_bwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
     "crdr_pixel_shuffle_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "crdr_pixel_shuffle_bwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "crdr_upsample16_cat_workspace": (_SZ, [C.POINTER(Upsample16Desc)]),
+    "crdr_upsample16_cat_fwd": (_I, [C.POINTER(Upsample16Desc), _P, _P, _P, _P]),
+    "crdr_upsample16_cat_bwd": (_I, [C.POINTER(Upsample16Desc), _P, _P, _P, _P, _SZ, _P]),
     "crdr_gauss_symbols": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _F, _I, _I, _I, _P, _P, _P]),
     "crdr_philox_fork": (_I, [_P, _P, C.c_uint64, _P]),
     "crdr_philox_uniform": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),

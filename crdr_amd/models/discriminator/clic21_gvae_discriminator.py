@@ -4,12 +4,17 @@ conv3 s2, conv3 head; LeakyReLU(0.2) fused into every conv but the head.  Parame
 
 `norm_type: CN` (clic21_gvae_discriminator.py:18-19) puts a ChannelNorm2D between conv and LeakyReLU on every block but the first:
 the conv runs without activation and the norm carries the fused LeakyReLU(0.2).  Keys as the reference's nn.Sequential numbers them:
-`model.0`, `model.2`, `model.3.{gamma,beta}`, `model.5`, `model.6.{gamma,beta}`, ..., `model.21.{gamma,beta}`, head `model.23`."""
+`model.0`, `model.2`, `model.3.{gamma,beta}`, `model.5`, `model.6.{gamma,beta}`, ..., `model.21.{gamma,beta}`, head `model.23`.
+
+CLIC21GVAELatentConditionalDiscriminator (clic21_gvae_discriminator.py:53-68) is the same trunk behind a condition on the quantised latent:
+`latent_conv.0` (1x1 conv + LeakyReLU(0.2) of y_hat.detach()), up-sampled x16 (bilinear, bicubic or nearest) and concatenated behind the
+image by one kernel (hip/functional.py upsample16_cat), so the trunk's first conv reads 3 + latent_nc channels."""
 from __future__ import annotations
 
 import torch.nn as nn
 
 from crdr_amd.hip import chain as CH
+from crdr_amd.hip import functional as HF
 from crdr_amd.models.layer.hific_norm import ChannelNorm2D
 from crdr_amd.models.layer.hip_layers import HipConv2d, to_image_nhwc
 from crdr_amd.utils.registry import DISCRIMINATOR_REGISTRY
@@ -87,17 +92,49 @@ class _BlocksCN(nn.Module):
         return getattr(self, str(self.head_idx))(x)
 
 
+def _trunk(in_ch, main_ch, out_ch, norm_type: str, num_downscale: int) -> nn.Module:
+    if norm_type == "CN":
+        return _BlocksCN(in_ch, main_ch, out_ch, 3, num_downscale)
+    if norm_type != "none":
+        raise NotImplementedError(f"norm_type {norm_type!r}: only 'none' (CRDR, config/crdr_stage_3.yaml:23) and 'CN' (ChannelNorm2D) "
+                                  "are built; 'BN' and 'IN' are not")
+    return _Blocks(in_ch, main_ch, out_ch, 3, num_downscale)
+
+
 @DISCRIMINATOR_REGISTRY.register()
 class CLIC21GVAEDiscriminator(BaseDiscriminator):
     def __init__(self, in_ch=3, out_ch=1, main_ch=64, norm_type: str = "BN", num_downscale: int = 4):
         super().__init__()
-        if norm_type == "CN":
-            self.model = _BlocksCN(in_ch, main_ch, out_ch, 3, num_downscale)
-            return
-        if norm_type != "none":
-            raise NotImplementedError(f"norm_type {norm_type!r}: only 'none' (CRDR, config/crdr_stage_3.yaml:23) and 'CN' (ChannelNorm2D) "
-                                      "are built; 'BN' and 'IN' are not")
-        self.model = _Blocks(in_ch, main_ch, out_ch, 3, num_downscale)
+        self.model = _trunk(in_ch, main_ch, out_ch, norm_type, num_downscale)
 
     def forward(self, input, **kwargs):
         return self.model(to_image_nhwc(input))
+
+
+@DISCRIMINATOR_REGISTRY.register()
+class CLIC21GVAELatentConditionalDiscriminator(BaseDiscriminator):
+    BATCH_INPUTS = ("y_hat",)   # per-sample keyword inputs: a trainer that stacks [x_hat; x] along the batch stacks these as well
+
+    def __init__(self, in_ch=3, out_ch=1, y_ch=192, latent_nc=12, main_ch=64, norm_type: str = "BN", latent_interp_mode: str = "bilinear"):
+        super().__init__()
+        assert latent_interp_mode in ["bilinear", "bicubic", "nearest"]
+        if in_ch != 3:
+            raise NotImplementedError(f"in_ch {in_ch}: the fused up-sample + concat kernel takes a 3-channel image")
+        if latent_nc % 4 != 0 or not 4 <= latent_nc <= 64:
+            raise NotImplementedError(f"latent_nc {latent_nc}: the fused up-sample + concat kernel takes a multiple of 4 in [4, 64]")
+        self.latent_conv = nn.Sequential()
+        self.latent_conv.add_module("0", HipConv2d(y_ch, latent_nc, 1))
+        self.model = _trunk(in_ch + latent_nc, main_ch, out_ch, norm_type, 4)
+        self.latent_interp_mode = latent_interp_mode
+
+    def forward(self, input, y_hat, **kwargs):
+        cond = getattr(self.latent_conv, "0")(y_hat.detach(), act="lrelu")
+        x = HF.upsample16_cat(to_image_nhwc(input), cond, self.latent_interp_mode)
+        # The trunk's input depends on a trainable layer (latent_conv), and a kept chain handle gives no gradient to the chain's input
+        # (chain.run_chain_reuse): reused in the discriminator phase it would drop latent_conv's gradient from the D(x_hat) term.  So this
+        # class hands out no handle, and the trainers take their one-pass [x_hat; x] path.
+        keep, CH.KEEP_HANDLES = CH.KEEP_HANDLES, None
+        try:
+            return self.model(x)
+        finally:
+            CH.KEEP_HANDLES = keep

@@ -34,6 +34,9 @@ class MultirateBetaCondHrrGanRateDistortionTrainer(BetaConditions, MultirateHigh
         # `reuse_d_forward` (default on): the discriminator phase takes D(x_hat) from the generator phase's forward instead of evaluating it again
         self.reuse_d_forward = bool(opt.get("reuse_d_forward", __import__("os").environ.get("CRDR_REUSE_D_FORWARD", "1") != "0"))
         self._init_conditions(opt)   # the (q, beta) draw: beta_conditions.py
+        # per-sample keyword inputs the discriminator's modules declare (`BATCH_INPUTS`: y_hat of CLIC21GVAELatentConditionalDiscriminator): the
+        # [x̂; x] pass stacks these along the batch.  A discriminator that declares none sees the launches it always had
+        self.d_batch_inputs = tuple(sorted({k for m in self.discriminator.modules() for k in getattr(m, "BATCH_INPUTS", ())}))
 
     # ------------------------------------------------------------------ G phase: forward, losses, backward
     def _g_forward(self, real, cond: Dict, noise, current_iter: int) -> Dict:
@@ -71,13 +74,18 @@ class MultirateBetaCondHrrGanRateDistortionTrainer(BetaConditions, MultirateHigh
             finally:
                 handles, _chain.KEEP_HANDLES = _chain.KEEP_HANDLES, None
             return out, (handles[0] if (on and handles is not None and len(handles) == 1) else None)
+        # D(x_hr) receives **other like D(x_hat): a discriminator conditioned on the latent reads the LOW-rate pass's y_hat for the high-rate
+        # image too, as the reference does (...beta_cond...trainer.py:56)
         with torch.no_grad():
             real_d, d_real_handle = d_keep(relative.detach(), keep and relative is real_p)
         fake_g, d_handle = d_keep(fake, keep)
         adv = (self.gan_loss.forward_diff(real_d, fake_g, is_real=False, is_disc=False)
                + self.gan_loss.forward_diff(fake_g, real_d, is_real=True, is_disc=False)) / 2
+        # the discriminator's keyword inputs for the discriminator phase (the reference passes **other_outputs there too, :92-98), detached
+        d_kwargs = {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in other.items()}
         return {"bpp": bpp, "other": other, "terms": {"distortion": dist_loss, "perceptual": percep, "adv": adv},
-                "nonrate": dist_loss + beta_t * (percep + adv), "extra": {"real": real_p, "fake": fake.detach(), "q": q, "d_handle": d_handle, "d_real_handle": d_real_handle}}
+                "nonrate": dist_loss + beta_t * (percep + adv),
+                "extra": {"real": real_p, "fake": fake.detach(), "q": q, "d_kwargs": d_kwargs, "d_handle": d_handle, "d_real_handle": d_real_handle}}
 
     def _seg_generator(self, real, cond: Dict, noise, current_iter: int) -> Dict:
         f = self._g_forward(real, cond, noise, current_iter)
@@ -95,19 +103,21 @@ class MultirateBetaCondHrrGanRateDistortionTrainer(BetaConditions, MultirateHigh
         backward do not read G's parameters, so running them BEFORE the G update is the same computation -- and lets
         them overlap the all-reduce of G's gradients."""
         q = ctx["q"]
+        kw = {**ctx["d_kwargs"], "rate_ind": q}
         self.discriminator.requires_grad_(True)
         self.d_optimizer.zero_grad(partitions=self._d_parts(q))
         if ctx.get("d_handle") is not None:
             # D(x_hat): the generator phase's forward (same weights, same input) -- nothing is launched, the backward runs on its activations
             fake_d = _chain.run_chain_reuse(ctx["d_handle"])[0]
             real_d = (_chain.run_chain_reuse(ctx["d_real_handle"])[0] if ctx.get("d_real_handle") is not None
-                      else self.discriminator(ctx["real"], rate_ind=q))
+                      else self.discriminator(ctx["real"], **kw))
         else:
             # one pass over [x̂; x] (the discriminator has no batch statistics -- norm_type none -- so this equals the
             # reference's two separate calls per sample) halves the launches and doubles the rows of every GEMM.  The rate-aware
             # discriminators (multirate_clic21_gvae_discriminator.py) keep no chain handle and always come here; their norm_type IN
             # takes its moments per image, so a sample's output does not depend on what else is in the batch either
-            both = self.discriminator(torch.cat([ctx["fake"], ctx["real"]], dim=0), rate_ind=q)
+            both_kw = {k: (torch.cat([v, v], dim=0) if k in self.d_batch_inputs else v) for k, v in kw.items()}
+            both = self.discriminator(torch.cat([ctx["fake"], ctx["real"]], dim=0), **both_kw)
             fake_d, real_d = both[: both.shape[0] // 2], both[both.shape[0] // 2:]
         l_d_real = self.gan_loss.forward_diff(real_d, fake_d.detach(), is_real=True, is_disc=True) * 0.5
         l_d_fake = self.gan_loss.forward_diff(fake_d, real_d.detach(), is_real=False, is_disc=True) * 0.5

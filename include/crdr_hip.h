@@ -649,6 +649,39 @@ int crdr_pixel_shuffle_fwd(const float* x, int ldx, int N, int H, int W, int C, 
 int crdr_pixel_shuffle_bwd(const float* dy, int lddy, int N, int H, int W, int C, float* dx, int lddx, crdr_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------ */
+/* x16 up-sampling fused with the concatenation behind the image (optional registered op: the          */
+/* reference's CLIC21GVAELatentConditionalDiscriminator, clic21_gvae_discriminator.py:53-68)           */
+/* ------------------------------------------------------------------------------------------------ */
+/* clic21_gvae_discriminator.py:66-68:  out = torch.cat((img, F.interpolate(cond, scale_factor=16, mode=..., align_corners=False)), dim=1)
+ * on NHWC memory.  img is [N][16h][16w] pixels of 3 channels at pixel stride ldi (the image layout: >= 4), cond is [N][h][w] pixels of
+ * Cc channels at pixel stride ldc, out is [N][16h][16w] pixels at pixel stride ldo >= Cc + 4 whose lanes are
+ *   [img0 img1 img2 | cond_0 .. cond_{Cc-1} | 0]
+ * -- the image lanes copied bit for bit, the pad lane written as an exact zero.  Per axis, output index 16 i + r (0 <= r < 16) reads
+ *   nearest (mode 0)   source i, weight 1
+ *   bilinear (mode 1)  f0 = i - 1, t = (r + 8.5) / 16 for r < 8;  f0 = i, t = (r - 7.5) / 16 for r >= 8;  sources f0, f0 + 1, weights 1 - t, t
+ *   bicubic (mode 2)   the same f0, t;  sources f0 - 1 .. f0 + 2 with the Keys weights (A = -0.75) c2(t + 1), c1(t), c1(1 - t), c2(2 - t),
+ *                      c1(x) = ((A + 2) x - (A + 3)) x^2 + 1,  c2(x) = ((A x - 5 A) x + 8 A) x - 4 A
+ * source indices clamped to the grid (clamped taps keep their weights), the 2-D weight the product of the two axes' -- torch's own
+ * arithmetic for these modes, in fp32.  Cc % 4 == 0, 4 <= Cc <= 64; strides in floats, multiples of 4; pointers 16-byte aligned; anything
+ * else is refused. */
+typedef struct crdr_upsample16_desc {
+  int32_t N, h, w;                 /* images, latent grid (the image is 16 h x 16 w) */
+  int32_t Cc;                      /* condition channels */
+  int32_t ldi, ldc, ldo;           /* pixel strides of the image (and dimg), the condition (and dcond) and the output (and dout) */
+  int32_t mode;                    /* 0 nearest, 1 bilinear, 2 bicubic */
+} crdr_upsample16_desc;
+/* bytes of the backward's workspace (the tiles' partial sums of dcond) */
+size_t crdr_upsample16_cat_workspace(const crdr_upsample16_desc* d);
+int crdr_upsample16_cat_fwd(const crdr_upsample16_desc* d, const float* img, const float* cond, float* out, crdr_stream_t s);
+/* its autograd from dout (pixel stride ldo):  dimg (pixel stride ldi) takes lanes 0..2 of dout bit for bit and a zero fourth lane;  dcond
+ * (pixel stride ldc) is the adjoint of the up-sampling.  Either may be NULL and is then not computed (generator phase: dimg alone, no
+ * workspace needed; discriminator phase: dcond alone).  No atomics: every tile folds its 16 rows and its columns in a fixed order into a
+ * partial per staged source, and one thread per element of dcond adds the partials that reach it in tile order -- two calls agree bit
+ * for bit. */
+int crdr_upsample16_cat_bwd(const crdr_upsample16_desc* d, const float* dout, float* dimg, float* dcond, void* ws, size_t ws_bytes,
+                            crdr_stream_t s);
+
+/* ------------------------------------------------------------------------------------------------ */
 /* losses                                                                                            */
 /* ------------------------------------------------------------------------------------------------ */
 /* out[0] (+)= sum (a-b)^2 ; backward da = 2 (a-b) g, db = -da   (distortion_loss.py:41-46)         */
