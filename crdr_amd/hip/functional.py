@@ -868,6 +868,40 @@ def maxpool3s2(x):
     return _MaxPool3s2.apply(x)
 
 
+class _MaxPool2s2(torch.autograd.Function):
+    """F.max_pool2d(x, 2, 2) on NHWC memory (crdr_maxpool2s2_fwd / _bwd): channel slices of wider tensors go in as they are.  x is saved;
+    the backward recomputes the argmax from it (first maximum in row-major order, torch's rule) and writes every element of dx once."""
+
+    @staticmethod
+    def forward(ctx, x):
+        lib = L.load()
+        x, ldx = ops.nhwc(x)
+        n, c, h, w = x.shape
+        if c % 4 != 0:
+            raise L.CrdrHipError(f"maxpool2s2: {c} channels are not a multiple of 4")
+        y = ops.empty_nhwc(n, c, h // 2, w // 2, x.device)
+        L.check(lib.crdr_maxpool2s2_fwd(x.data_ptr(), ldx, n, h, w, c, y.data_ptr(), c, ops._stream()), "maxpool2s2_fwd")
+        ctx.save_for_backward(x)
+        ctx.ldx = ldx
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        lib = L.load()
+        n, c, h, w = x.shape
+        dy, lddy = ops.nhwc(dy)
+        dx = ops.empty_nhwc(n, c, h, w, x.device)
+        L.check(lib.crdr_maxpool2s2_bwd(x.data_ptr(), ctx.ldx, dy.data_ptr(), lddy, n, h, w, c, dx.data_ptr(), c, ops._stream()),
+                "maxpool2s2_bwd")
+        return dx
+
+
+def maxpool2s2(x):
+    """F.max_pool2d(x, 2, 2) for NHWC tensors with C % 4 == 0, H >= 2 and W >= 2; autograd routes as torch does."""
+    return _MaxPool2s2.apply(x)
+
+
 class _LpipsLayer(torch.autograd.Function):
     """(f_real, f_fake, lin[C]) -> per-image distance [N]; gradient flows to f_fake only."""
 

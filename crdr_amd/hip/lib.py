@@ -220,6 +220,8 @@ SIGNATURES = {
     "crdr_adam_step_dyn": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _P, _P, _F, _P]),
     "crdr_maxpool3s2_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "crdr_maxpool3s2_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "crdr_maxpool2s2_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "crdr_maxpool2s2_bwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P]),
     "crdr_lpips_layer_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
     "crdr_lpips_layer_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "crdr_pmf_to_quantized_cdf": (_I, [_P, _I, _I, _P]),

@@ -754,10 +754,24 @@ int crdr_adam_step_dyn(float* p, const float* g, float* m, float* v, int64_t n, 
                        const float* dyn, const float* sqnorm, float max_norm, crdr_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------ */
-/* LPIPS helpers (perceptual_loss.py:25-30; lpips 0.1.4 AlexNet)                                      */
+/* LPIPS helpers (perceptual_loss.py:25-30; lpips 0.1.4 AlexNet and VGG16)                            */
 /* ------------------------------------------------------------------------------------------------ */
 int crdr_maxpool3s2_fwd(const float* x, float* y, int N, int H, int W, int C, crdr_stream_t s);
 int crdr_maxpool3s2_bwd(const float* x, const float* dy, float* dx, int N, int H, int W, int C, crdr_stream_t s);
+/* nn.MaxPool2d(kernel_size=2, stride=2) on NHWC memory: the pools between the conv groups of lpips 0.1.4 pretrained_networks.vgg16 /
+ * torchvision vgg16.features (indices 4, 9, 16, 23).  x is [N][H][W] pixels of C channels at pixel stride ldx, y is [N][H/2][W/2] pixels
+ * at pixel stride ldy (floor: an odd last row / column is dropped, ceil_mode=False),
+ *   y[n][oh][ow][c] = max over i,j in {0,1} of x[n][2oh+i][2ow+j][c]
+ * with torch's replacement rule (a later value wins when it is strictly greater, or a NaN).  C % 4 == 0; strides are in floats, multiples
+ * of 4 and at least C (channel slices of wider NHWC tensors); pointers 16-byte aligned; H >= 2 and W >= 2; N and ceil(H/2) at most 65535.
+ * Anything else is refused with an error code. */
+int crdr_maxpool2s2_fwd(const float* x, int ldx, int N, int H, int W, int C, float* y, int ldy, crdr_stream_t s);
+/* its autograd: dx[n][2oh+i][2ow+j][c] = dy[n][oh][ow][c] where (i, j) is the window's first maximum in the scan order (0,0), (0,1),
+ * (1,0), (1,1) under the rule above (an all-equal window sends its gradient to (0,0)), 0 at every other pixel, those of a dropped odd row
+ * or column included.  The argmax is recomputed from x; every element of dx (pixel stride lddx) is written exactly once, no atomics, no
+ * memset: the result depends only on the arguments.  dx must not overlap x or dy.  The same refusals. */
+int crdr_maxpool2s2_bwd(const float* x, int ldx, const float* dy, int lddy, int N, int H, int W, int C, float* dx, int lddx,
+                        crdr_stream_t s);
 /* per-pixel: d = sum_c lin[c] * (f0/|f0| - f1/|f1|)^2 ; out[n] += mean_pixels d */
 /* ws: N*64 floats */
 int crdr_lpips_layer_fwd(const float* f0, const float* f1, const float* lin, int N, int HW, int C, float* out,

@@ -1,12 +1,12 @@
 """Distortion metrics over a folder of reconstructions (the PSNR / LPIPS part of the reference's
 scripts/calc_metrics.py:119-192; FID / KID / DISTS need third-party networks and are out of scope):
 
-    python scripts/calc_metrics.py --real_dir kodak --fake_dir out [--metrics psnr lpips] [--lpips_weights alex.pth] [-d cuda:0]
+    python scripts/calc_metrics.py --real_dir kodak --fake_dir out [--metrics psnr lpips] [--lpips_net alex|vgg] [--lpips_weights f.pth] [-d cuda:0]
 
 PSNR follows the reference exactly: images are read back as uint8 RGB (what `imwrite` truncated to), the squared error is
 taken in float32, PSNR is computed PER IMAGE (20 log10 255 - 10 log10 mse) and the per-image values are averaged
-(calc_metrics.py:146,168).  LPIPS (AlexNet) runs on the GPU through the HIP LPIPS path used in training, on [-1, 1]
-images, `lpips(fake, real)` per image, averaged."""
+(calc_metrics.py:146,168).  LPIPS (AlexNet by default, VGG16 with `--lpips_net vgg`) runs on the GPU through the HIP LPIPS path
+used in training, on [-1, 1] images, `lpips(fake, real)` per image, averaged."""
 import argparse
 import json
 import os
@@ -42,12 +42,12 @@ def avg_psnr(real_paths, fake_paths) -> float:
     return float(np.mean([psnr_one(read_rgb_f32(r), read_rgb_f32(f)) for r, f in zip(real_paths, fake_paths)]))
 
 
-def avg_lpips(real_paths, fake_paths, device: str, weights=None) -> float:
+def avg_lpips(real_paths, fake_paths, device: str, weights=None, lpips_net: str = "alex") -> float:
     import torch
-    from crdr_amd.losses.perceptual_loss import LpipsAlex
-    net = LpipsAlex().to(device)
+    from crdr_amd.losses.perceptual_loss import LPIPS_NETS
+    net = LPIPS_NETS[lpips_net]().to(device)
     if weights:
-        net.load_lpips_file(weights)  # {"alexnet_features": sd, "lpips_lin": sd}, see crdr_amd/losses/perceptual_loss.py
+        net.load_lpips_file(weights)  # {"alexnet_features" | "vgg16_features": sd, "lpips_lin": sd}, see crdr_amd/losses/perceptual_loss.py
     else:
         print("warning: no --lpips_weights given, LPIPS runs on randomly initialised weights", file=sys.stderr)
     net.eval()
@@ -65,6 +65,7 @@ def main(argv=None):
     ap.add_argument("--real_dir", required=True)
     ap.add_argument("--fake_dir", required=True)
     ap.add_argument("--metrics", nargs="+", default=["psnr"], choices=["psnr", "lpips"])
+    ap.add_argument("--lpips_net", default="alex", choices=["alex", "vgg"])
     ap.add_argument("--lpips_weights", default=None)
     ap.add_argument("-d", "--device", default="cuda:0")
     ap.add_argument("--out", default=None, help="write the result dict as json")
@@ -74,7 +75,7 @@ def main(argv=None):
     if "psnr" in a.metrics:
         res["PSNR"] = avg_psnr(real, fake)
     if "lpips" in a.metrics:
-        res["LPIPS"] = avg_lpips(real, fake, a.device, a.lpips_weights)
+        res["LPIPS"] = avg_lpips(real, fake, a.device, a.lpips_weights, a.lpips_net)
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:

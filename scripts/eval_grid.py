@@ -1,13 +1,13 @@
 """(q, beta) grid evaluation in the layout of the reference's rd_results/*.csv (README.md:52-58,76; rd_results/README.md):
 
     python scripts/eval_grid.py --config_path config/crdr.yaml --model_path crdr.pth.tar --img_dir ./kodak \
-        --dataset kodak --out_csv rd_results/kodak.csv [--qualities 0 0.25 ... 4] [--betas 3.84 0] [--lpips_weights f]
+        --dataset kodak --out_csv rd_results/kodak.csv [--qualities 0 0.25 ... 4] [--betas 3.84 0] [--lpips_net alex|vgg] [--lpips_weights f]
 
 For every quality q (default 0, 0.25, ..., 4: 17 levels) each image is compressed ONCE -- the bitstream does not depend on
 beta (kodak.csv rows beta = 0 and 3.84 carry identical bpp) -- and decoded once per beta.  Per (q, beta) row:
 `dataset,quality,beta,bpp,PSNR,LPIPS,DISTS` with bpp = mean over images of 8 * bytes(.bin) / (H W) (scripts/compress.py:
 108-121), PSNR = mean over images of the per-image PSNR of the uint8-truncated PNGs (scripts/calc_metrics.py:119-168),
-LPIPS through the HIP LPIPS-Alex when weights are supplied (else empty), DISTS empty (third-party network, out of scope).
+LPIPS through the HIP LPIPS net (`--lpips_net`: alex by default, or vgg) when weights are supplied (else empty), DISTS empty (third-party network, out of scope).
 With `--reference_csv rd_results/kodak.csv` the result is compared row by row with the published numbers (bpp +-1e-4,
 PSNR +-0.01 dB: BASELINE.json's gate) -- meaningful once the pretrained checkpoint is supplied."""
 import argparse
@@ -99,6 +99,7 @@ def main(argv=None):
     ap.add_argument("--out_csv", required=True)
     ap.add_argument("--qualities", type=float, nargs="+", default=None)
     ap.add_argument("--betas", type=float, nargs="+", default=[3.84, 0.0])
+    ap.add_argument("--lpips_net", default="alex", choices=["alex", "vgg"])
     ap.add_argument("--lpips_weights", default=None)
     ap.add_argument("--reference_csv", default=None)
     ap.add_argument("-d", "--device", default="cuda:0")
@@ -116,8 +117,8 @@ def main(argv=None):
     model.codec_setup()
     lp = None
     if a.lpips_weights:
-        from crdr_amd.losses.perceptual_loss import LpipsAlex
-        lp = LpipsAlex().to(a.device).eval()
+        from crdr_amd.losses.perceptual_loss import LPIPS_NETS
+        lp = LPIPS_NETS[a.lpips_net]().to(a.device).eval()
         lp.load_lpips_file(a.lpips_weights)
     paths = sorted(glob(os.path.join(a.img_dir, "*.png")))
     assert paths, f"no .png images under {a.img_dir}"
