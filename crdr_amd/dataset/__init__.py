@@ -1,7 +1,9 @@
 """Input pipeline. The hot path is benchmarked on device-resident synthetic crops; the
 folder datasets reproduce the reference's tensor contract -- {'real_images': float32 [N,3,256,256] in [-1,1]}
 from RandomCrop(256, reflect pad if needed) + HFlip(0.5) + ToTensor + Normalize(0.5, 0.5)
-(src/dataset/data_transform.py:19-45, base_dataset.py:30-34) -- without torchvision."""
+(src/dataset/data_transform.py:19-45, base_dataset.py:30-34) -- without torchvision; with `resize_range` set,
+PilRandomResize (data_transform.py:54-73) runs in front of the crop, by PIL on the host path and by
+crdr_resize_crop_flip_normalize on the device-pool path."""
 from __future__ import annotations
 
 import os
@@ -49,17 +51,31 @@ def _to_tensor(img: np.ndarray) -> torch.Tensor:
 class _FolderDataset(Dataset):
     exts = ("*.png", "*.jpg", "*.jpeg", "*.JPEG")
 
-    def __init__(self, root_dir: str, is_train: bool, image_size: int = 256, subset_list=None, **_):
+    def __init__(self, root_dir: str, is_train: bool, image_size: int = 256, subset_list=None, resize_range=None,
+                 interpolation: str = "bicubic", **_):
         dirs = [os.path.join(root_dir, str(s)) for s in subset_list] if (is_train and subset_list and
                                                                          os.path.isdir(os.path.join(root_dir, str(subset_list[0])))) else [root_dir]
         self.paths = sorted(p for d in dirs for e in self.exts for p in glob(os.path.join(d, e)))
         self.is_train, self.size = is_train, image_size
+        # PilRandomResize in front of the crop (data_transform.py:29-33, 54-73); evaluation ignores both keys (PilEvalTransform)
+        self.resize_range = tuple(float(f) for f in resize_range) if (is_train and resize_range is not None) else None
+        if self.resize_range is not None:
+            from PIL import Image
+            self.resample = dict(bicubic=Image.BICUBIC, bilinear=Image.BILINEAR)[interpolation]
 
     def __len__(self):
         return len(self.paths)
 
+    def _random_resize(self, path: str) -> np.ndarray:
+        from PIL import Image
+        img = Image.open(path).convert("RGB")
+        w, h = img.size
+        low = max(float(self.size) / float(min(h, w)), self.resize_range[0])
+        scale = np.random.uniform(low, max(low, self.resize_range[1]))
+        return np.array(img.resize((int(w * scale), int(h * scale)), self.resample), dtype=np.uint8)
+
     def __getitem__(self, i: int) -> Dict[str, torch.Tensor]:
-        img = _load_rgb(self.paths[i])
+        img = _load_rgb(self.paths[i]) if self.resize_range is None else self._random_resize(self.paths[i])
         if self.is_train:
             s = self.size
             ph, pw = max(0, s - img.shape[0]), max(0, s - img.shape[1])
@@ -108,7 +124,8 @@ def build_loaders(opt, device) -> Tuple[object, Optional[DataLoader]]:
         o = {k: v for k, v in dict(tr).items() if k != "device_pool"}
         paths = build_dataset(o, True).paths
         train = DeviceCropLoader(DeviceImagePool.from_paths(paths, device), bs, int(o.get("image_size", 256)),
-                                 seed=int(opt.get("data_seed", 0)), rank=_D.rank(), world_size=_D.world_size())
+                                 seed=int(opt.get("data_seed", 0)), rank=_D.rank(), world_size=_D.world_size(),
+                                 resize_range=o.get("resize_range", None), interpolation=o.get("interpolation", "bicubic"))
     else:
         from crdr_amd.trainer import dist as _D
         dset = build_dataset(tr, True)

@@ -182,6 +182,7 @@ SIGNATURES = {
     "crdr_spectral_norm_fwd": (_I, [_P, _I, _I, _P, _P, _I, C.c_float, _P, _P, _P, _SZ, _P]),
     "crdr_spectral_norm_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _SZ, _P]),
     "crdr_crop_flip_normalize": (_I, [_P, _P, _I, _I, _I, _P, _I, _P]),
+    "crdr_resize_crop_flip_normalize": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P]),
     "crdr_linear_fwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     "crdr_linear_bwd": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
     "crdr_linear_group_fwd": (_I, [_P, _I, _I, _I, _P, _I, _P]),

@@ -377,6 +377,19 @@ int crdr_spectral_norm_bwd(const float* dw_sn, const float* w, const float* u, c
 int crdr_crop_flip_normalize(const uint8_t* pool, const int64_t* items, int N, int crop_h, int crop_w, float* out, int ldo,
                              crdr_stream_t s);
 
+/* The same pipeline with PilRandomResize in front (data_transform.py:19-73: the whole image resized by PIL's 8-bit bicubic / bilinear
+ * resampler, then RandomCrop -> HFlip -> ToTensor -> Normalize): only the crop window of the resized image is computed, bit-equal to PIL.
+ * The host resolves the filter, the reflect padding of the RESIZED image and the flip into two integer tables per sample (22-bit
+ * fixed-point coefficients, PIL's normalize_coeffs_8bpc); the kernel does
+ *   mid = clip8((2^21 + sum_i kh[i][c] * src[y][xlo[c] + i]) >> 22),  b = clip8((2^21 + sum_j kv[j][r] * mid[ylo[r] + j][c]) >> 22)
+ * per channel in 32-bit integers and writes ((float)b / 255.0f - 0.5f) / 0.5f.  A pass PIL skips is cnt = 1, k = 2^22.
+ * items: DEVICE int32 [N][4] = {byte offset of the image in pool: low 32 bits, high 32 bits; H; W}.
+ * tabs:  DEVICE int32, per sample the column table [2 + ktaps][crop_w] then the row table [2 + ktaps][crop_h]; the rows of a table are
+ *        lo, cnt (<= ktaps), k[0], ..., k[ktaps - 1] (entries past cnt are not read).  1 <= ktaps <= 17.
+ * out: as crdr_crop_flip_normalize (NHWC fp32, pixel stride ldo >= 4, a multiple of 4, 16-byte aligned, channel 3 zeroed). */
+int crdr_resize_crop_flip_normalize(const uint8_t* pool, const int32_t* items, const int32_t* tabs, int N, int ktaps, int crop_h,
+                                    int crop_w, float* out, int ldo, crdr_stream_t s);
+
 /* Linear layer on a handful of row vectors (M <= 16: the beta-conditioning MLP and the per-block projections of the
  * [1, 512] conditioning vector, elic_interpca_beta_cond_autoencoder.py:42-84, fourier_cond.py:12-37) -- a 1x1 conv
  * over M pixels is launch-latency bound on the implicit-GEMM path, these run as GEMV-style kernels on the raw [O][I]
