@@ -243,8 +243,9 @@ __global__ __launch_bounds__(256) void wgrad_reduce(const float* ws, float* g, i
 // input channels j x ALL T taps: the slab is read in 256-byte row segments (j contiguous), the sums go through LDS and
 // leave as ONE contiguous run of 64 T floats of the parameter gradient g[i][j0 .. j0+63][0 .. T) -- both sides fully
 // coalesced (a direct j-fastest mapping writes 4-byte pieces T floats apart and re-touches every output line T times).
-// RGB jobs (smallj: slab rows are [T][4]) keep 256 consecutive outputs per tile.  Tile count per job (host side):
-// smallj ? ceil(gI gJ T / 256) : gI * ceil(gJ / 64).  Splits are summed in a fixed order (deterministic).
+// RGB jobs (smallj: slab rows are [T][4]) and jobs with more taps than the LDS tile holds (T > kRedMaxT: 7x7, 11x11) keep
+// 256 consecutive outputs per tile and add their splits in split order.  Tile count per job (host side):
+// (smallj || T > 32) ? ceil(gI gJ T / 256) : gI * ceil(gJ / 64).  Splits are summed in a fixed order (deterministic).
 // Batched kernels find the table entry of a work unit by binary search over the prefix sums.  From global memory that is a
 // chain of ~log2(n) dependent loads (4-6 us) per unit -- more than the unit's own traffic takes for small layers -- so a
 // workgroup first copies the prefix table (n <= kPrefixCache entries, totals < 2^31) to LDS.
